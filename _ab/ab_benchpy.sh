@@ -3,7 +3,7 @@
 set -euo pipefail
 for rep in 1 2 3; do
   for b in "$@"; do
-    out=$(timeout -k 10 120 python "$b" --no-cpu-baseline --no-extras --steps 50 2>/dev/null)
+    out=$(timeout -k 10 120 python "$b" --full --no-cpu-baseline --no-extras --steps 50 2>/dev/null)
     python -c "import json,sys; d=json.loads(sys.argv[1]); print(sys.argv[2], d['value'], d['ms_per_step'], round(sum(d['stages_ms'].values()), 4))" "$out" "$b"
   done
 done

@@ -9,7 +9,7 @@ for rep in 1 2; do
   for arg in "$@"; do
     d=${arg%%:*}; l=${arg#*:}
     if [ "$l" = "-" ]; then lib=$ROOT/$d/newsrecommendationsystem_amd/libnrms_hip.so; else lib=$ROOT/$l; fi
-    out=$(cd "$ROOT/$d" && NRMS_LIB_PATH=$lib timeout -k 10 120 python bench.py --no-cpu-baseline --no-extras --steps 30 2>/dev/null)
+    out=$(cd "$ROOT/$d" && NRMS_LIB_PATH=$lib timeout -k 10 120 python bench.py --full --no-cpu-baseline --no-extras --steps 30 2>/dev/null)
     python -c "import json,sys; d=json.loads(sys.argv[1]); print(sys.argv[2], d['value'], d['stages_ms'])" "$out" "$arg"
   done
 done

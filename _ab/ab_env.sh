@@ -4,7 +4,7 @@
 set -euo pipefail
 for rep in 1 2 3; do
   for e in "$@"; do
-    out=$(env $e timeout -k 10 120 python bench.py --no-cpu-baseline --no-extras --steps 30 2>/dev/null)
+    out=$(env $e timeout -k 10 120 python bench.py --full --no-cpu-baseline --no-extras --steps 30 2>/dev/null)
     python -c "import json,sys; d=json.loads(sys.argv[1]); print(repr(sys.argv[2]), d['value'], d['ms_per_step'], d['stages_ms'])" "$out" "$e"
   done
 done

@@ -1,6 +1,11 @@
 """NRMS scoring throughput on MI355X (BASELINE.json metric / config 3).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 1024] [--proj folded|direct|auto]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last timed
+step's logits under --dump-outputs and prints the headline line; every other
+measurement and check (see "Extra fields" below) runs only with --full.
 
 One step = one full NRMS forward (src/model/NRMS/__init__.py:19-48, eval
 mode) over a batch of B synthetic MIND-shaped impressions resident in HBM:
@@ -14,7 +19,7 @@ user shard every step (weak scaling, no data-path collective); with --stream
 the ranks score the whole stream once (config 4, strong scaling). The time
 is the max over ranks. Rank 0 prints one JSON line.
 
-Extra fields: per-stage milliseconds (HIP events on the launch stream), the
+Extra fields (--full): per-stage milliseconds (HIP events on the launch stream), the
 roofline of the dominant kernel, and the CPU baseline (oracle ATen-order
 restatement timed on this host, kind "port") with a parity check of the GPU
 logits against it on the same sample.
@@ -412,9 +417,31 @@ def n_all_titles(B):
 
 
 def run_steps(fwd, batches, steps, events=None):
+    """`steps` forwards over the batches in turn; the last step's logits."""
+    y = None
     for k in range(steps):
         cand, clk = batches[k % len(batches)]
-        fwd.run(cand, clk, events[k] if events else None)
+        y = fwd.run(cand, clk, events[k] if events else None)
+    return y
+
+
+DUMP_MAX_BYTES = 64 << 20
+SETTLE_S = 0.05   # least duration of the warm-up on the timed path (main())
+
+
+def dump_outputs(path, name, y, world=1):
+    """Write what the last timed step returned (its logits, [B, 1+K] fp32) to
+    path/name.npy. The default batch gives 20 KB per rank; only a --batch
+    beyond 3.3 M impressions (over all ranks) passes the 64 MB that the dump
+    may take in all, and then each rank keeps a fixed, seeded sample of rows."""
+    import numpy as np
+    a = y.detach().float().cpu().numpy()
+    cap = DUMP_MAX_BYTES // world
+    if a.nbytes > cap:
+        rows = np.random.default_rng(0).choice(a.shape[0], cap // a[0].nbytes, replace=False)
+        a = a[np.sort(rows)]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _free_port():
@@ -508,22 +535,33 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None,
                     help="timed steps (default 50; with --stream: every batch of the shard)")
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=10,
+                    help="un-timed steps before the graph capture, and again on the timed path right before "
+                         "the timed steps (there for at least 50 ms)")
     ap.add_argument("--batch", type=int, default=1024, help="impressions per GPU per step")
     ap.add_argument("--proj", choices=["folded", "direct", "auto"], default="folded")
     ap.add_argument("--stream", action="store_true",
                     help="BASELINE cfg4: score the whole user-sharded 2M-impression stream once "
                          "(strong scaling; --steps is then the number of batches, 0 = all)")
     ap.add_argument("--stream-impressions", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the forward-path equality check, the eager loop, the per-stage "
+                         "pass and roofline, the FedAvg sync leg (multi-rank), the gather / config-2 / direct "
+                         "/ GEMM-arithmetic figures, the FedAvg quality run, the CPU baseline with parity and "
+                         "AUC, and the evaluate() throughput (each with its own --no-... switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the logits the last timed step produced to "
+                         "DIR/logits.npy (float32; rank r of a multi-rank run: DIR/logits.rank<r>.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the CPU-port leg (and the CPU-side AUC check and the FedAvg quality run)")
+                    help="--full: skip the CPU-port leg (and the CPU-side AUC check and the FedAvg quality run)")
     ap.add_argument("--no-quality", action="store_true",
-                    help="skip the reference-scale FedAvg quality run (quality.run_scaled, ~20 s)")
+                    help="--full: skip the reference-scale FedAvg quality run (quality.run_scaled, ~20 s)")
     ap.add_argument("--as-shard", default=None, metavar="R/W",
                     help="without a process group, take rank R of W's user shard of the stream (tests: a "
                          "single-rank run of one shard of a multi-rank job)")
     ap.add_argument("--unfused", action="store_true", help="separate MHSA / additive / pool kernels")
-    ap.add_argument("--no-extras", action="store_true", help="skip the gather / config-2 / direct figures")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip the gather / config-2 / direct figures")
     ap.add_argument("--no-graph", action="store_true", help="time the eager call loop instead of a HIP graph replay")
     ap.add_argument("--inflight", type=int, default=1,
                     help="batches in flight: that many captured forwards (own workspace, logits and stream) "
@@ -544,6 +582,9 @@ def main():
     args = ap.parse_args()
     if args.no_cpu_baseline:
         args.no_quality = True
+    if args.steps is not None and args.steps < (0 if args.stream else 1):
+        ap.error("--steps must be at least 1")
+    full_run = args.full
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: start one (a child, before any GPU call)
@@ -593,8 +634,9 @@ def main():
     tail = [b for b in batches if b[0].shape[0] != B]
     # the timed step is the product path itself (nrms_forward, stage events
     # inside the library); ForwardPlan (the stage ABI, one call per stage)
-    # gives the per-stage algorithmic work and the --unfused stage kernels
-    plan = ForwardPlan(model, B, C, N_CLICKED, L, proj_mode=mode, fused=not args.unfused)
+    # gives the per-stage algorithmic work (--full) and the --unfused stage kernels
+    plan = (ForwardPlan(model, B, C, N_CLICKED, L, proj_mode=mode, fused=not args.unfused)
+            if full_run or args.unfused else None)
     fwd = plan if args.unfused else TimedForward(model, B, C, N_CLICKED, L, proj_mode=mode)
     tail_fwd = None
     if tail:
@@ -612,22 +654,24 @@ def main():
         run_steps(fwd, full, args.warmup)
         if tail_fwd is not None:
             tail_fwd.run(*tail[0])
-        # one un-timed check: the timed path, the module's forward and the
-        # stage-by-stage plan give bitwise the same logits
-        y_fwd = fwd.run(cand, clk).clone()
-        y_mod = model.forward_ids(cand, clk, proj_mode=mode)
-        y_plan = plan.run(cand, clk).clone()
-        same = bool(torch.equal(y_fwd, y_mod)) and (args.unfused or bool(torch.equal(y_fwd, y_plan)))
-        # the stage breakdown comes from a separate pass with per-stage events:
-        # an event between two kernels costs a few us of queue time (the empty
-        # stage between two back-to-back events measures ~4.7 us), so the timed
-        # steps run the product path without them
-        n_ev = min(steps, 50)
-        events = (fwd.make_events(n_ev) if not args.unfused else
-                  [[torch.cuda.Event(enable_timing=True) for _ in range(n_st + 1)] for _ in range(n_ev)])
+        same = None
+        if full_run:
+            # one un-timed check: the timed path, the module's forward and the
+            # stage-by-stage plan give bitwise the same logits
+            y_fwd = fwd.run(cand, clk).clone()
+            y_mod = model.forward_ids(cand, clk, proj_mode=mode)
+            y_plan = plan.run(cand, clk).clone()
+            same = bool(torch.equal(y_fwd, y_mod)) and (args.unfused or bool(torch.equal(y_fwd, y_plan)))
+            # the stage breakdown comes from a separate pass with per-stage events:
+            # an event between two kernels costs a few us of queue time (the empty
+            # stage between two back-to-back events measures ~4.7 us), so the timed
+            # steps run the product path without them
+            n_ev = min(steps, 50)
+            events = (fwd.make_events(n_ev) if not args.unfused else
+                      [[torch.cuda.Event(enable_timing=True) for _ in range(n_st + 1)] for _ in range(n_ev)])
         # One batch repeated (not --stream): the step is captured once into a
         # HIP graph (the C ABI is capturable: no allocation, no sync) and
-        # replayed, as a serving loop would; the eager loop is timed beside it.
+        # replayed, as a serving loop would; --full times the eager loop beside it.
         graph = None
         graphs, gstreams = [], []
         if not args.unfused and not args.stream and len(full) == 1 and not args.no_graph:
@@ -640,36 +684,54 @@ def main():
                 f.logits.fill_(float("nan"))     # the replay must recompute them
                 g.replay()
                 torch.cuda.synchronize()
-                same = same and bool(torch.equal(f.logits, y_fwd))
+                if full_run:
+                    same = same and bool(torch.equal(f.logits, y_fwd))
                 graphs.append(g)
                 gstreams.append(torch.cuda.Stream(device))
             graph = graphs[0]
         eager_ms = None
-        if graph is not None:
+        if graph is not None and full_run:
             torch.cuda.synchronize()
             te = time.perf_counter()
             run_steps(fwd, full, steps)
             torch.cuda.synchronize()
             eager_ms = (time.perf_counter() - te) / steps * 1e3
-        torch.cuda.synchronize()
+        def issue(n):
+            """n steps of the timed path; the logits buffer of the last one."""
+            if graph is not None and len(graphs) > 1:
+                cur = torch.cuda.current_stream(device)
+                for st in gstreams:
+                    st.wait_stream(cur)
+                for k in range(n):
+                    with torch.cuda.stream(gstreams[k % len(graphs)]):
+                        graphs[k % len(graphs)].replay()
+                return fwds[(n - 1) % len(graphs)].logits
+            if graph is not None:
+                for _ in range(n):
+                    graph.replay()
+                return fwd.logits
+            return run_steps(fwd, full, n)
+
+        # the warm-up ends on the timed path itself, right before the clock
+        # starts: the graph capture above leaves the GPU idle, and the first
+        # ~1.5 ms of steps after such a gap run slow (measured: +1 % on a
+        # 200-step window). The W warm-up steps again, for at least SETTLE_S.
+        tw = time.perf_counter()
+        settle_steps = 0
+        while True:
+            issue(max(args.warmup, 1))
+            settle_steps += max(args.warmup, 1)
+            torch.cuda.synchronize()
+            if time.perf_counter() - tw >= SETTLE_S:
+                break
+        settle_ms = (time.perf_counter() - tw) * 1e3
         if dist:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        if graph is not None and len(graphs) > 1:
-            cur = torch.cuda.current_stream(device)
-            for st in gstreams:
-                st.wait_stream(cur)
-            for k in range(steps):
-                with torch.cuda.stream(gstreams[k % len(graphs)]):
-                    graphs[k % len(graphs)].replay()
-        elif graph is not None:
-            for _ in range(steps):
-                graph.replay()
-        else:
-            run_steps(fwd, full, steps)
+        y_last = issue(steps)
         if args.stream and tail_fwd is not None and steps == len(full):
-            tail_fwd.run(*tail[0])
+            y_last = tail_fwd.run(*tail[0])
         torch.cuda.synchronize()
         if dist:
             dist.barrier()
@@ -679,6 +741,10 @@ def main():
         from newsrecommendationsystem_amd.distributed import max_over_ranks
         elapsed = max_over_ranks(elapsed, device)
 
+    if args.dump_outputs:
+        # what the last timed step left in its logits buffer, before anything
+        # else runs on that forward
+        dump_outputs(args.dump_outputs, "logits" if world == 1 else f"logits.rank{rank}", y_last, world)
     if args.dump_logits:
         # untimed: every batch of this rank's shard once, logits by impression
         # index -- from the timed path itself (the captured graph's replay when
@@ -695,6 +761,71 @@ def main():
         n_done = sum(y.shape[0] for y in ys)
         np.savez(f"{args.dump_logits}.rank{rank}.npz", idx=idx[:n_done].cpu().numpy(),
                  logits=torch.cat(ys).float().cpu().numpy())
+    ms_per_step = elapsed / steps * 1e3
+    if args.stream:
+        done = (steps * B + (tail[0][0].shape[0] if tail and steps == len(full) else 0))
+        if dist:
+            from newsrecommendationsystem_amd.distributed import sum_over_ranks
+            done = sum_over_ranks(done, device)
+        value = done / elapsed
+    else:
+        value = world * B * steps / elapsed
+    workload = ("BASELINE cfg4: full NRMS forward over the whole user-sharded stream "
+                f"({idx.numel() if not dist else 'per-rank shards of'} impressions"
+                f"{'' if dist else ' on this GPU'}), every title's vector produced (all-padding "
+                "history titles encoded once per batch, see titles)"
+                if args.stream else
+                "BASELINE cfg3: full NRMS forward scoring (news+user encoder+click predictor), "
+                "every title's vector produced (all-padding history titles encoded once per batch, see "
+                "titles); batch = first B impressions of this rank's cfg4 user shard")
+    # the headline: all a plain run prints (--full adds its fields to it below)
+    head = {
+        "metric": METRIC, "value": round(value, 1), "unit": "impressions/s", "n_gpus": world,
+        "steps": steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": "strong" if args.stream else "weak", "vs_baseline": None,
+        "dtype": {"f32": "fp32",
+                  "x6": "fp32 (GEMMs: exact 3-way bf16 split, 6 products, fp32 accumulate)",
+                  "f16x3": "fp32 (additive GEMM: 2-plane fp16 split, 22-bit operands, 3 products, fp32 "
+                           "accumulate, out-of-fp16-range groups recomputed x6; Q|K|V projections: "
+                           "power-of-two-scaled fp16 split, A in 3 pieces, W 22-bit, 3 products (4 where a W column "
+                           "fits in 11 bits), fp32 "
+                           "accumulate; UserEncoder additive GEMM: power-of-two-scaled 2-plane fp16 split, 3 products)"}[args.gemm],
+        "data": "synthetic (MIND-shaped stream: counter-hash ids, random-init weights, N(0,1) embedding table)",
+        "warmup_on_timed_path": {"steps": settle_steps, "ms": round(settle_ms, 2), "at_least_ms": SETTLE_S * 1e3,
+                                 "note": "un-timed steps of the timed path right before the timed ones "
+                                         "(--warmup steps, repeated for at least at_least_ms)"},
+        "config": {"workload": workload, "global_batch": B * world,
+                   "impressions_per_gpu": B, "candidates": C, "clicked": N_CLICKED,
+                   "title_len": L, "vocab": V_WORDS, "d_model": D, "heads": 15,
+                   "query_dim": 200, "proj_mode": args.proj, "gemm_arith": args.gemm,
+                   "news_tail": "unfused" if args.unfused else "fused",
+                   "stream": {"impressions": args.stream_impressions or S.N_IMPRESSIONS,
+                              "users": S.N_USERS, "sharding": "user_id % world"},
+                   "parallelism": f"user-shard x{world}",
+                   "batches_in_flight": max(1, len(graphs))},
+        "timed_path": (("nrms_forward (one C-ABI call) captured once in a HIP graph, replayed per step"
+                        + (f"; {len(graphs)} batches in flight (--inflight: {len(graphs)} captured forwards, "
+                           "each with its own workspace, logits and stream, replayed in turn; every step "
+                           "still runs the whole forward of one batch)" if len(graphs) > 1 else ""))
+                       if graph is not None else
+                       "nrms_forward_timed without events (one C-ABI call per step)") if not args.unfused
+                      else "ForwardPlan stage kernels (--unfused)",
+        "graph_replay": graph is not None,
+        "process_group": None if not dist else dist.get_backend(),
+        "world_size": dist.get_world_size() if dist else 1,
+        "launcher": os.environ.get("NRMS_BENCH_LAUNCHER",
+                                   "torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ else "none"),
+        "full": full_run,
+    }
+    if args.as_shard:
+        head["config"]["as_shard"] = args.as_shard
+    if not full_run:
+        head["cpu_baseline"] = None
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
     # config 5's collective (the FedAvg parameter all-reduce over the group),
     # after the timed region: a multi-rank run measures its xGMI cost too
     fedavg = fedavg_sync_leg(model, device, dist) if dist else None
@@ -750,15 +881,6 @@ def main():
     else:
         achieved, peak, unit, bound = w["bytes"] / t_dom / 1e9, PEAK_HBM_GBS, "GB/s", "hbm"
 
-    ms_per_step = elapsed / steps * 1e3
-    if args.stream:
-        done = (steps * B + (tail[0][0].shape[0] if tail and steps == len(full) else 0))
-        if dist:
-            from newsrecommendationsystem_amd.distributed import sum_over_ranks
-            done = sum_over_ranks(done, device)
-        value = done / elapsed
-    else:
-        value = world * B * steps / elapsed
     # every stage's floors (instruction issue, algorithmic bytes at 8 TB/s),
     # the binding one and the fraction of it achieved; their sum is the step's
     stage_floor = {}
@@ -801,35 +923,8 @@ def main():
             "flop_split": w["split"]}
     if sq is not None:
         roofline["sq_counters"] = sq
-    workload = ("BASELINE cfg4: full NRMS forward over the whole user-sharded stream "
-                f"({idx.numel() if not dist else 'per-rank shards of'} impressions"
-                f"{'' if dist else ' on this GPU'}), every title's vector produced (all-padding "
-                "history titles encoded once per batch, see titles)"
-                if args.stream else
-                "BASELINE cfg3: full NRMS forward scoring (news+user encoder+click predictor), "
-                "every title's vector produced (all-padding history titles encoded once per batch, see "
-                "titles); batch = first B impressions of this rank's cfg4 user shard")
-    out = {
-        "metric": METRIC, "value": round(value, 1), "unit": "impressions/s", "n_gpus": world,
-        "steps": steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": "strong" if args.stream else "weak", "vs_baseline": None,
-        "dtype": {"f32": "fp32",
-                  "x6": "fp32 (GEMMs: exact 3-way bf16 split, 6 products, fp32 accumulate)",
-                  "f16x3": "fp32 (additive GEMM: 2-plane fp16 split, 22-bit operands, 3 products, fp32 "
-                           "accumulate, out-of-fp16-range groups recomputed x6; Q|K|V projections: "
-                           "power-of-two-scaled fp16 split, A in 3 pieces, W 22-bit, 3 products (4 where a W column "
-                           "fits in 11 bits), fp32 "
-                           "accumulate; UserEncoder additive GEMM: power-of-two-scaled 2-plane fp16 split, 3 products)"}[args.gemm],
-        "data": "synthetic (MIND-shaped stream: counter-hash ids, random-init weights, N(0,1) embedding table)",
-        "config": {"workload": workload, "global_batch": B * world,
-                   "impressions_per_gpu": B, "candidates": C, "clicked": N_CLICKED,
-                   "title_len": L, "vocab": V_WORDS, "d_model": D, "heads": 15,
-                   "query_dim": 200, "proj_mode": args.proj, "gemm_arith": args.gemm,
-                   "news_tail": "unfused" if args.unfused else "fused",
-                   "stream": {"impressions": args.stream_impressions or S.N_IMPRESSIONS,
-                              "users": S.N_USERS, "sharding": "user_id % world"},
-                   "parallelism": f"user-shard x{world}",
-                   "batches_in_flight": max(1, len(graphs))},
+    out = dict(head)
+    out.update({
         "roofline": roofline,
         "titles": {"per_step": n_titles, "all_padding": n_pad, "encoded": n_enc,
                    "rows_encoded": news_rows[0], "rows_if_uncompacted": n_enc * L,
@@ -855,27 +950,13 @@ def main():
                        f"projection (qkv_news): 'score' is then an empty event pair, 'user_fused' "
                        f"includes the scoring",
         "user_rows_projected": n_user,
-        "timed_path": (("nrms_forward (one C-ABI call) captured once in a HIP graph, replayed per step"
-                        + (f"; {len(graphs)} batches in flight (--inflight: {len(graphs)} captured forwards, "
-                           "each with its own workspace, logits and stream, replayed in turn; every step "
-                           "still runs the whole forward of one batch)" if len(graphs) > 1 else ""))
-                       if graph is not None else
-                       "nrms_forward_timed without events (one C-ABI call per step)") if not args.unfused
-                      else "ForwardPlan stage kernels (--unfused)",
         "eager": None if eager_ms is None else {
             "ms_per_step": round(eager_ms, 4), "impressions_per_s": round(B / (eager_ms / 1e3), 1),
             "note": "the same call issued from Python every step (no graph)"},
         "forward_paths_bitwise_equal": same,
-        "graph_replay": graph is not None,
-        "process_group": None if not dist else dist.get_backend(),
-        "world_size": dist.get_world_size() if dist else 1,
-        "launcher": os.environ.get("NRMS_BENCH_LAUNCHER",
-                                   "torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ else "none"),
-    }
+    })
     if fedavg is not None:
         out["fedavg_sync"] = fedavg
-    if args.as_shard:
-        out["config"]["as_shard"] = args.as_shard
     if rank == 0 and world == 1 and not args.no_extras and not args.stream:
         out["gather_roofline"] = gather_hbm(device)
         out["news_encoder_cfg2"] = news_encoder_cfg2(model, device)

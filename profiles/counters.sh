@@ -3,7 +3,7 @@
 set -euo pipefail
 STAGE=$1; TAG=$2; shift 2
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
-OUT=$REPO/gpurun_out/pmc_${TAG}_${STAGE}
+OUT=$REPO/${NRMS_OUT_DIR:-results}/pmc_${TAG}_${STAGE}   # (NRMS_OUT_DIR: relative to the repo root)
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 DRV=("$REPO/profiles/kernel_driver.py" "$STAGE" --iters 5 "$@")

@@ -1,8 +1,10 @@
 """Probe: bench.py with another history length (measurement only, not the
 headline workload). NRMS_PROBE_CLICKED=n sets the clicked titles per
-impression; the rest of the command line is bench.py's.
+impression; the rest of the command line is bench.py's (a plain run prints
+the headline line; the stage times need --full, which the two --no-...
+switches then trim).
 
-    NRMS_PROBE_CLICKED=32 python profiles/probes/bench_clicked.py --no-cpu-baseline --no-extras
+    NRMS_PROBE_CLICKED=32 python profiles/probes/bench_clicked.py --full --no-cpu-baseline --no-extras
 """
 import os
 import sys

@@ -100,7 +100,7 @@ def test_bench_two_ranks_stream_matches_one_rank(tmp_path):
     every impression's logits equal the single-rank run's bitwise (the batch
     an impression lands in never changes its logits)."""
     n = 20000
-    common = ["--stream", "--stream-impressions", str(n), "--no-extras", "--no-cpu-baseline", "--warmup", "1"]
+    common = ["--stream", "--stream-impressions", str(n), "--warmup", "1"]
     one = subprocess.run([sys.executable, "-u", "bench.py", *common, "--dump-logits", str(tmp_path / "one")],
                          cwd=ROOT, capture_output=True, text=True, timeout=400)
     assert one.returncode == 0, one.stderr[-3000:]
@@ -241,7 +241,7 @@ def test_bench_two_ranks_weak_graph_gloo(tmp_path):
     port = _free_port()
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
-                          "--dist-backend", "gloo", "--steps", "5", "--warmup", "2", "--no-extras",
+                          "--dist-backend", "gloo", "--steps", "5", "--warmup", "2", "--full", "--no-extras",
                           "--no-cpu-baseline", "--dump-logits", str(tmp_path / "two")],
                          cwd=ROOT, capture_output=True, text=True, timeout=400)
     _check_weak_record(two, 2, "gloo")
@@ -266,7 +266,8 @@ def test_bench_gpus2_self_launch_gloo(tmp_path):
     `--as-shard r/2`'s single-process run of its shard."""
     B = 1024
     two = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--dist-backend", "gloo", "--steps", "5",
-                          "--warmup", "2", "--no-extras", "--no-cpu-baseline", "--dump-logits", str(tmp_path / "two")],
+                          "--warmup", "2", "--full", "--no-extras", "--no-cpu-baseline",
+                          "--dump-logits", str(tmp_path / "two")],
                          cwd=ROOT, capture_output=True, text=True, timeout=600,
                          env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     rec = _check_weak_record(two, 2, "gloo")
@@ -277,7 +278,7 @@ def test_bench_gpus2_self_launch_gloo(tmp_path):
     assert fa["world"] == 2 and fa["params"] == 21955400 and fa["fedavg_sync_ms"] > 0
     for r in range(2):
         shard = subprocess.run([sys.executable, "bench.py", "--as-shard", f"{r}/2", "--steps", "2", "--warmup", "1",
-                                "--no-extras", "--no-cpu-baseline", "--dump-logits", str(tmp_path / f"s{r}")],
+                                "--dump-logits", str(tmp_path / f"s{r}")],
                                cwd=ROOT, capture_output=True, text=True, timeout=400)
         assert shard.returncode == 0, shard.stderr[-3000:]
         got, ref = np.load(tmp_path / f"two.rank{r}.npz"), np.load(tmp_path / f"s{r}.rank0.npz")
@@ -292,7 +293,7 @@ def test_bench_gpus2_nccl_on_one_gpu_is_fatal():
     import torch
     if torch.cuda.device_count() >= 2:
         pytest.skip("more than one GPU visible")
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--no-extras", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2"],
                        cwd=ROOT, capture_output=True, text=True, timeout=200,
                        env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert p.returncode != 0 and "needs 2 GPUs" in p.stderr, p.stderr[-2000:]
@@ -309,7 +310,7 @@ def test_bench_rccl_world1_weak_graph(tmp_path):
     port = _free_port()
     one = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "1",
-                          "--init-dist", "--dist-backend", "nccl", "--steps", "5", "--warmup", "2",
+                          "--init-dist", "--dist-backend", "nccl", "--steps", "5", "--warmup", "2", "--full",
                           "--no-extras", "--no-cpu-baseline", "--dump-logits", str(tmp_path / "rccl")],
                          cwd=ROOT, capture_output=True, text=True, timeout=400)
     rec = _check_weak_record(one, 1, "nccl")
@@ -330,7 +331,7 @@ def test_bench_as_shard_equals_rank_shard(tmp_path):
     """bench.py --as-shard 1/2 (one process, no group) scores shard 1 of 2:
     the graph-replayed logits equal the in-process run of that shard."""
     one = subprocess.run([sys.executable, "-u", "bench.py", "--as-shard", "1/2", "--steps", "3", "--warmup", "1",
-                          "--no-extras", "--no-cpu-baseline", "--dump-logits", str(tmp_path / "s")],
+                          "--dump-logits", str(tmp_path / "s")],
                          cwd=ROOT, capture_output=True, text=True, timeout=400)
     assert one.returncode == 0, one.stderr[-3000:]
     rec = json.loads([ln for ln in one.stdout.splitlines() if ln.startswith("{")][0])
@@ -341,6 +342,76 @@ def test_bench_as_shard_equals_rank_shard(tmp_path):
     assert np.array_equal(got["logits"].view(np.uint32), ref.view(np.uint32))
 
 
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_last_step_outputs(tmp_path):
+    """A plain `bench.py --steps N --warmup W --dump-outputs DIR`: N timed
+    steps, a headline line with ms_per_step and none of --full's legs, and
+    DIR/logits.npy = the float32 logits of the last timed step, bitwise the
+    graph replay's (--dump-logits) and the in-process run's of that batch."""
+    one = subprocess.run([sys.executable, "-u", "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "out"), "--dump-logits", str(tmp_path / "dl")],
+                         cwd=ROOT, capture_output=True, text=True, timeout=200)
+    assert one.returncode == 0, one.stderr[-3000:]
+    lines = [ln for ln in one.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, one.stdout[-3000:]
+    rec = json.loads(lines[0])
+    _check_plain_record(rec, 3, 1)
+    got = np.load(tmp_path / "out" / "logits.npy")
+    assert got.dtype == np.float32 and got.shape == (1024, 5) and np.isfinite(got).all()
+    assert os.listdir(tmp_path / "out") == ["logits.npy"]
+    assert np.array_equal(got.view(np.uint32), np.load(tmp_path / "dl.rank0.npz")["logits"].view(np.uint32))
+    _, ref = _shard_logits(0, 1, 1024)
+    assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+
+
+def _check_plain_record(rec, steps, warmup):
+    assert rec["steps"] == steps and rec["warmup"] == warmup and rec["full"] is False
+    assert rec["metric"].startswith("impressions/sec scored") and rec["dtype"].startswith("fp32")
+    assert rec["ms_per_step"] > 0 and rec["unit"] == "impressions/s" and rec["higher_is_better"] is True
+    assert abs(rec["value"] - 1024 / (rec["ms_per_step"] / 1e3)) <= 1e-3 * rec["value"]
+    w = rec["warmup_on_timed_path"]
+    assert w["steps"] >= warmup and w["ms"] >= w["at_least_ms"] == 50
+    for leg in ("stages_ms", "roofline", "eager", "gemm_legs", "parity_vs_cpu", "eval_throughput"):
+        assert leg not in rec
+
+
+def test_bench_steps_sets_the_timed_replays(tmp_path, monkeypatch, capsys):
+    """bench.main() in this process, graph replays counted: one after the
+    capture, the warm-up on the timed path (its count is in the line) and
+    exactly --steps timed ones; two runs with different --steps dump the
+    same logits bitwise (same inputs from run to run, each replay recomputes
+    the whole forward)."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    calls = []
+    real = torch.cuda.CUDAGraph.replay
+
+    def counted(self):
+        calls.append(1)
+        return real(self)
+
+    monkeypatch.setattr(torch.cuda.CUDAGraph, "replay", counted)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    dumps = []
+    for n in (3, 7):
+        del calls[:]
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", str(n), "--warmup", "2",
+                                          "--dump-outputs", str(tmp_path / f"out{n}")])
+        with torch.random.fork_rng(devices=[0]):   # bench seeds the global generators
+            bench.main()
+        lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        _check_plain_record(rec, n, 2)
+        assert rec["graph_replay"] is True
+        assert len(calls) == 1 + rec["warmup_on_timed_path"]["steps"] + n
+        dumps.append(np.load(tmp_path / f"out{n}" / "logits.npy"))
+    assert np.isfinite(dumps[0]).all()
+    assert np.array_equal(dumps[0].view(np.uint32), dumps[1].view(np.uint32))
+
+
 @pytest.mark.timeout(600)
 def test_bench_rccl_world1(tmp_path):
     """bench.py's multi-rank path with RCCL, on one GPU: torch.distributed.run
@@ -349,7 +420,7 @@ def test_bench_rccl_world1(tmp_path):
     all-reduce and the stream-count SUM); one JSON line, every impression of
     the sampled stream scored, logits equal to the run without a group."""
     n = 8192
-    common = ["--stream", "--stream-impressions", str(n), "--no-extras", "--no-cpu-baseline", "--warmup", "1"]
+    common = ["--stream", "--stream-impressions", str(n), "--warmup", "1"]
     port = _free_port()
     one = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "1",

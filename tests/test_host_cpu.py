@@ -210,15 +210,23 @@ def test_bench_gpus_n_nccl_without_gpus_is_fatal():
     itself; under the nccl backend it first needs 2 visible GPUs and exits
     non-zero, with a message, when it has fewer (here: none), before any rank
     starts or any GPU call is made."""
-    p = _bench(["--gpus", "2", "--no-extras", "--no-cpu-baseline"])
+    p = _bench(["--gpus", "2"])
     assert p.returncode != 0
     assert "needs 2 GPUs" in p.stderr, p.stderr[-2000:]
+    assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_bench_zero_timed_steps_is_fatal():
+    """--steps sets the number of timed steps; none cannot give ms_per_step."""
+    p = _bench(["--gpus", "1", "--steps", "0", "--warmup", "1"])
+    assert p.returncode != 0
+    assert "--steps must be at least 1" in p.stderr, p.stderr[-2000:]
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
 
 
 def test_bench_world_size_mismatch_is_fatal():
     """A launcher whose process count differs from --gpus is an error, not a
     warning (the record would otherwise claim the wrong GPU count)."""
-    p = _bench(["--gpus", "1", "--no-extras"], env={"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
+    p = _bench(["--gpus", "1"], env={"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert p.returncode != 0
     assert "WORLD_SIZE=2 but --gpus=1" in p.stderr, p.stderr[-2000:]
