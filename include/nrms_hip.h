@@ -56,7 +56,14 @@ extern "C" {
 /* 7: host-side readers of the eval split files (nrms_behaviors_scan /
  *    nrms_behaviors_parse / nrms_news_parse); nrms_forward's workspace holds
  *    the UserEncoder dispatch order (nrms_forward_workspace_size grew). */
-#define NRMS_ABI_VERSION 8
+/* 8: deterministic training backward (workspaces of nrms_additive_backward /
+ *    nrms_qkv_project_backward; nrms_embedding_backward_ws). */
+/* 9: nrms_recommend_topk / nrms_recommend_topk_workspace_size. Recorded here
+ *    as well, since it went in under 8 without a bump: nrms_embedding_backward_ws
+ *    sums an id with more than 256 tokens in 64-token segments added in
+ *    segment order (round 6), no longer in one token-order chain; ids with
+ *    <= 256 tokens are unchanged. */
+#define NRMS_ABI_VERSION 9
 
 typedef enum {
   NRMS_OK = 0,
@@ -315,6 +322,50 @@ int32_t nrms_score(const float* news, int64_t B, int32_t C, int64_t stride_b,
 int32_t nrms_score_pairs(const float* news, int64_t n_news, const float* user, int64_t n_users,
                          const int64_t* news_idx, const int64_t* user_idx, int64_t n_pairs,
                          int32_t D, float* out, hipStream_t stream);
+
+/* (ABI 9) Catalogue-wide recommendation, the end use of the reference's
+ * recommend() (src/recommend.py:352-386, which ranks 20 randomly drawn
+ * candidates): for every user the K best rows of the whole news table, the
+ * rows of exclude[u, :] (the user's history) left out. One fused kernel scores
+ * users x news on the matrix cores and keeps a running top-K per user, so the
+ * [n_users, n_news] score matrix is never written (topk.hip).
+ *   - out_score[u, j] = <news[out_idx[u, j]], user[u]> at fp32-GEMM accuracy,
+ *     in the arithmetic of nrms_get_gemm_arith at enqueue time: F32 exact fp32
+ *     products, SPLIT_BF16X6 and SPLIT_F16X3 both the exact split-bf16 x6 (no
+ *     fp16 planes: the vectors carry no range guarantee). A zero score is
+ *     returned as +0. An infinite operand scores NaN in the split modes.
+ *   - Per user the entries are sorted by (score descending, row ascending):
+ *     np.argsort(-y, kind="stable"). (The reference's np.argsort(-y),
+ *     recommend.py:340, leaves ties unspecified.)
+ *   - A NaN score ranks after every number, -inf included, as numpy's sort
+ *     places it; NaNs order among themselves by row.
+ *   - Rows listed in exclude[u, :] ([n_users, n_excl] row-major, or NULL with
+ *     n_excl = 0) are never returned for user u. An entry outside [0, n_news)
+ *     is ignored and never read through (negative padding, or the len(corpus)
+ *     row of PADDED_NEWS); duplicates are allowed.
+ *   - When fewer than K rows are eligible the tail is out_idx = -1,
+ *     out_score = NaN.
+ *   - The result for user u depends only on user[u], exclude[u, :], news and
+ *     K, bit for bit: not on n_users, on the other users of the call, on the
+ *     chunking or on the grid (a score's accumulation order is a function of k
+ *     only), and the first K entries do not depend on K.
+ *   - Limits: D = 300, 1 <= K <= 256, 0 <= n_excl <= 256, n_news < 2^31, news
+ *     and user 16-byte aligned (workspace 8-byte); anything else returns
+ *     NRMS_ERR_UNSUPPORTED (the size function: 0). Null pointers or negative
+ *     sizes: NRMS_ERR_INVALID_ARG. n_users == 0 is a successful no-op;
+ *     n_news == 0 fills the padding values. A workspace smaller than
+ *     nrms_recommend_topk_workspace_size(...): NRMS_ERR_WORKSPACE.
+ *   - The workspace holds 512 (K + n_excl <= 128) or 1024 candidate keys of 8
+ *     bytes per user and news chunk; the chunk count (1 for many users, up to
+ *     64 for few) follows from the shapes, or from NRMS_TOPK_CHUNK = news rows
+ *     per chunk in the environment (read once).
+ *   - No allocation, no synchronisation, capturable into a hipGraph. */
+size_t nrms_recommend_topk_workspace_size(int64_t n_users, int64_t n_news, int32_t D, int32_t K,
+                                          int32_t n_excl);
+int32_t nrms_recommend_topk(const float* news, int64_t n_news, const float* user, int64_t n_users,
+                            int32_t D, const int64_t* exclude, int32_t n_excl, int32_t K,
+                            int64_t* out_idx, float* out_score, void* workspace, size_t workspace_bytes,
+                            hipStream_t stream);
 
 /* Per-impression ranking metrics (src/evaluate.py:24-42,160-168) over ragged
  * impressions: impression i owns scores/labels [offsets[i], offsets[i+1]).

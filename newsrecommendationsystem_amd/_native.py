@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must precede the CDLL load: shared HIP runtime)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NRMS_LIB_PATH") or os.path.join(_PKG, "libnrms_hip.so")   # override: A/B builds
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 NRMS_PROJ_AUTO, NRMS_PROJ_DIRECT, NRMS_PROJ_FOLDED = 0, 1, 2
 NRMS_GEMM_SPLIT_BF16X6, NRMS_GEMM_F32, NRMS_GEMM_SPLIT_F16X3 = 0, 1, 2
@@ -71,6 +71,8 @@ SIGNATURES = {
     "nrms_score": (_i32, [_p, _i64, _i32, _i64, _i64, _p, _i64, _i32, _p, _p]),
     "nrms_score_pairs": (_i32, [_p, _i64, _p, _i64, _p, _p, _i64, _i32, _p, _p]),
     "nrms_impression_metrics": (_i32, [_p, _p, _p, _i64, _p, _p]),
+    "nrms_recommend_topk_workspace_size": (_sz, [_i64, _i64, _i32, _i32, _i32]),
+    "nrms_recommend_topk": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _p, _p, _p, _sz, _p]),
     # training kernels
     "nrms_dropout": (_i32, [_p, _p, _i64, ctypes.c_float, ctypes.c_uint64, _p]),
     "nrms_additive_forward_train": (_i32, [_p, _i64, _i32, _EW, _p, _p, _p, _p]),

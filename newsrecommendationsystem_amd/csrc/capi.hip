@@ -499,6 +499,29 @@ int32_t nrms_score_pairs(const float* news, int64_t n_news, const float* user, i
   return launch_score_pairs(news, n_news, user, n_users, news_idx, user_idx, n_pairs, D, out, stream);
 }
 
+size_t nrms_recommend_topk_workspace_size(int64_t n_users, int64_t n_news, int32_t D, int32_t K,
+                                          int32_t n_excl) {
+  if (n_users < 0 || n_news < 0 || n_news > INT32_MAX || D != 300 || K < 1 || K > 256 || n_excl < 0 ||
+      n_excl > 256)
+    return 0;
+  return topk_workspace_bytes(n_users, n_news, K, n_excl);
+}
+
+int32_t nrms_recommend_topk(const float* news, int64_t n_news, const float* user, int64_t n_users,
+                            int32_t D, const int64_t* exclude, int32_t n_excl, int32_t K,
+                            int64_t* out_idx, float* out_score, void* workspace, size_t workspace_bytes,
+                            hipStream_t stream) {
+  if (n_news < 0 || n_users < 0 || n_excl < 0) return NRMS_ERR_INVALID_ARG;
+  if (D != 300 || K < 1 || K > 256 || n_excl > 256 || n_news > INT32_MAX) return NRMS_ERR_UNSUPPORTED;
+  if (n_users == 0) return NRMS_OK;
+  if (!user || !out_idx || !out_score || !workspace || (n_news > 0 && !news) || (n_excl > 0 && !exclude))
+    return NRMS_ERR_INVALID_ARG;
+  if (((uintptr_t)news % 16) != 0 || ((uintptr_t)user % 16) != 0 || ((uintptr_t)workspace % 8) != 0)
+    return NRMS_ERR_UNSUPPORTED;
+  return launch_topk(news, n_news, user, n_users, exclude, n_excl, K, out_idx, out_score, workspace,
+                     workspace_bytes, stream);
+}
+
 int32_t nrms_impression_metrics(const float* scores, const int32_t* labels,
                                 const int64_t* offsets, int64_t n_imp, double* out,
                                 hipStream_t stream) {

@@ -360,6 +360,13 @@ int32_t launch_user_row_list(const PaddingGroups& pg, int64_t n_rows, int64_t* l
 int32_t launch_score_pairs(const float* news, int64_t n_news, const float* user, int64_t n_users,
                            const int64_t* news_idx, const int64_t* user_idx, int64_t n_pairs,
                            int D, float* out, hipStream_t s);
+// Catalogue-wide top-K (topk.hip): the K best news rows per user by
+// (score descending, row ascending), exclude[u, :] dropped; the contract is
+// nrms_recommend_topk's (nrms_hip.h). D = 300 only.
+size_t topk_workspace_bytes(int64_t n_users, int64_t n_news, int K, int n_excl);
+int32_t launch_topk(const float* news, int64_t n_news, const float* user, int64_t n_users,
+                    const int64_t* exclude, int n_excl, int K, int64_t* out_idx, float* out_score,
+                    void* ws, size_t ws_bytes, hipStream_t s);
 int32_t launch_impression_metrics(const float* scores, const int32_t* labels,
                                   const int64_t* offsets, int64_t n_imp, double* out,
                                   hipStream_t s);
