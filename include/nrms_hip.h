@@ -62,7 +62,11 @@ extern "C" {
  *    as well, since it went in under 8 without a bump: nrms_embedding_backward_ws
  *    sums an id with more than 256 tokens in 64-token segments added in
  *    segment order (round 6), no longer in one token-order chain; ids with
- *    <= 256 tokens are unchanged. */
+ *    <= 256 tokens are unchanged.
+ *    ABI 9, added later (additive, no bump): nrms_forward_state_t,
+ *    nrms_forward_state_size, nrms_forward_prepare,
+ *    nrms_forward_prepared_workspace_size (and _folded_), nrms_forward_prepared
+ *    and nrms_forward_prepared_timed. */
 #define NRMS_ABI_VERSION 9
 
 typedef enum {
@@ -407,6 +411,77 @@ int32_t nrms_forward_timed(const int64_t* cand_ids, const int64_t* clicked_ids, 
                            int32_t proj_mode, float* logits, void* workspace, size_t workspace_bytes,
                            hipStream_t stream, hipEvent_t* stage_events, int32_t n_events);
 const char* nrms_forward_stage_name(int32_t stage);
+
+/* (ABI 9, added later) The forward with its weight-derived state prepared once.
+ *
+ * nrms_forward recomputes, in every call, data that depends on the weights
+ * alone: both encoders' split Q|K|V weights, both packed W_add (with the news
+ * kernel's zero / NaN rows) and, in the folded mode, the projected vocabulary
+ * [V][nrms_qkv_row_stride(D)]. Between two parameter updates those are bitwise
+ * the same from call to call. nrms_forward_prepare enqueues exactly that work
+ * (the same launches on the same inputs, so the same bits) into a caller-owned
+ * state buffer, and nrms_forward_prepared runs the rest of the step against
+ * it: everything that reads a token id (the titles' classification, the news
+ * vectors, the user rows, the scores) still runs in every call. The logits are
+ * bitwise nrms_forward's under the same arithmetic, dedupe and compaction
+ * settings.
+ *
+ *   - The caller owns the buffer (nrms_forward_state_size bytes, 256-B aligned)
+ *     and the nrms_forward_state_t that describes it; the library allocates
+ *     nothing and keeps no pointer. With with_folded_table the table is the
+ *     first V * nrms_qkv_row_stride(D) floats of the buffer.
+ *   - The state is invalid once any parameter it was made from (the embedding
+ *     table, either encoder's W_Q / W_K / W_V weight or bias, either W_add
+ *     weight) changes, or under another GEMM arithmetic: the caller prepares
+ *     again (into the same buffer if captured graphs read it). b_add and q_add
+ *     are read by the step itself.
+ *   - Under NRMS_GEMM_F32 there are no packs: the state holds the folded table
+ *     only and the step packs W_add as nrms_forward does.
+ *   - A step only reads the state, so any number of forwards (other batch
+ *     sizes, other streams) may share one; everything a step writes lives in
+ *     its own workspace. Stream order is the caller's: the prepare must have
+ *     completed, or precede the step on its stream.
+ *   - nrms_forward_prepare never synchronises and can be captured in a graph.
+ *   - nrms_forward_prepared_workspace_size does not depend on V (the table is
+ *     not in the workspace); it covers every projection mode, the per-token
+ *     rows of the direct mode included. A call that resolves to the folded
+ *     mode needs nrms_forward_prepared_folded_workspace_size only.
+ *   - table is read in the direct mode only (it may be null otherwise).
+ *   - NRMS_ERR_INVALID_ARG, with nothing launched: state null, prepared for
+ *     another V or D or under another arithmetic than the current one, or
+ *     without a folded table on a call that resolves to the folded mode.
+ *     NRMS_ERR_WORKSPACE: a state buffer or workspace that is too small.
+ *   - Stages and event positions as nrms_forward_timed; qkv_news holds the
+ *     classification launches (folded) or the per-token projection (direct). */
+#define NRMS_STATE_FOLDED_TABLE 1   /* flags of nrms_forward_state_t */
+#define NRMS_STATE_QKV_PACKS 2
+#define NRMS_STATE_ADD_PACKS 4
+typedef struct {
+  void* buffer;        /* device pointer of the state buffer               */
+  size_t bytes;        /* its size                                         */
+  int64_t V;           /* vocabulary rows it was prepared for              */
+  int32_t D;
+  int32_t ld_qkv;      /* q|k|v row stride of the folded table (floats)    */
+  int32_t gemm_arith;  /* nrms_gemm_arith_t it was prepared under          */
+  int32_t flags;       /* NRMS_STATE_*: what the buffer holds              */
+} nrms_forward_state_t;
+size_t nrms_forward_state_size(int64_t V, int32_t D, int32_t with_folded_table);
+int32_t nrms_forward_prepare(const float* table, int64_t V, const nrms_encoder_weights_t* news_w,
+                             const nrms_encoder_weights_t* user_w, int32_t with_folded_table, void* state_buf,
+                             size_t state_bytes, nrms_forward_state_t* state, hipStream_t stream);
+size_t nrms_forward_prepared_workspace_size(int64_t B, int32_t C, int32_t N, int32_t L, int32_t D);
+size_t nrms_forward_prepared_folded_workspace_size(int64_t B, int32_t C, int32_t N, int32_t L, int32_t D);
+int32_t nrms_forward_prepared(const int64_t* cand_ids, const int64_t* clicked_ids, int64_t B, int32_t C,
+                              int32_t N, int32_t L, const float* table, int64_t V,
+                              const nrms_encoder_weights_t* news_w, const nrms_encoder_weights_t* user_w,
+                              int32_t proj_mode, float* logits, void* workspace, size_t workspace_bytes,
+                              hipStream_t stream, const nrms_forward_state_t* state);
+int32_t nrms_forward_prepared_timed(const int64_t* cand_ids, const int64_t* clicked_ids, int64_t B, int32_t C,
+                                    int32_t N, int32_t L, const float* table, int64_t V,
+                                    const nrms_encoder_weights_t* news_w, const nrms_encoder_weights_t* user_w,
+                                    int32_t proj_mode, float* logits, void* workspace, size_t workspace_bytes,
+                                    hipStream_t stream, const nrms_forward_state_t* state,
+                                    hipEvent_t* stage_events, int32_t n_events);
 
 /* ---------------------------------------------------------------------------
  * Training kernels: the train-mode forward pieces and the backward of the path

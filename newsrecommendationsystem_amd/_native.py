@@ -35,6 +35,16 @@ class EncoderWeights(ctypes.Structure):
 
 _EW = ctypes.POINTER(EncoderWeights)
 
+
+class ForwardState(ctypes.Structure):
+    """nrms_forward_state_t (filled by nrms_forward_prepare)."""
+    _fields_ = [("buffer", _p), ("bytes", _sz), ("V", _i64), ("D", _i32), ("ld_qkv", _i32),
+                ("gemm_arith", _i32), ("flags", _i32)]
+
+
+_FS = ctypes.POINTER(ForwardState)
+NRMS_STATE_FOLDED_TABLE, NRMS_STATE_QKV_PACKS, NRMS_STATE_ADD_PACKS = 1, 2, 4
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "nrms_abi_version": (_i32, []),
@@ -95,6 +105,14 @@ SIGNATURES = {
     "nrms_forward_timed": (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _i64, _EW, _EW, _i32, _p, _p,
                                   _sz, _p, _p, _i32]),
     "nrms_forward_stage_name": (ctypes.c_char_p, [_i32]),
+    "nrms_forward_state_size": (_sz, [_i64, _i32, _i32]),
+    "nrms_forward_prepare": (_i32, [_p, _i64, _EW, _EW, _i32, _p, _sz, _FS, _p]),
+    "nrms_forward_prepared_workspace_size": (_sz, [_i64, _i32, _i32, _i32, _i32]),
+    "nrms_forward_prepared_folded_workspace_size": (_sz, [_i64, _i32, _i32, _i32, _i32]),
+    "nrms_forward_prepared": (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _i64, _EW, _EW, _i32, _p, _p,
+                                     _sz, _p, _FS]),
+    "nrms_forward_prepared_timed": (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _i64, _EW, _EW, _i32, _p, _p,
+                                           _sz, _p, _FS, _p, _i32]),
     # host-side readers (HOST pointers)
     "nrms_behaviors_scan": (_i32, [_p, _i64, _p]),
     "nrms_behaviors_parse": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

@@ -169,14 +169,14 @@ int32_t encode_from_qkv(const float* qkv, int64_t ldq, int64_t n_rows, const int
                         hipStream_t s, float* wap = nullptr, bool* deduped = nullptr,
                         int64_t broadcast_from = 0, int64_t* user_list = nullptr, int64_t user_rows = 0,
                         bool prepacked = false, bool direct_rows = false, bool* classified = nullptr,
-                        bool preclassified = false) {
+                        bool preclassified = false, float* step_ws = nullptr) {
   const int D = w->d_model;
   if (deduped) *deduped = false;
   if (classified) *classified = false;
   if (wap && fused_news_supported(L, D, w->n_heads, w->query_dim))
     return launch_fused_news(qkv, ldq, n_rows, ids_a, n_seq_a, ids_b, n_seq, w->w_add, w->b_add,
                              w->q_add, wap, out, s, -1, deduped, broadcast_from, user_list, user_rows,
-                             prepacked, direct_rows, -1, classified, preclassified);
+                             prepacked, direct_rows, -1, classified, preclassified, step_ws);
   if (preclassified) return NRMS_ERR_INVALID_ARG;
   if (direct_rows) ids_a = ids_b = nullptr;   // per-token rows: the ids only classify (fused kernel)
   // stage kernels: any row stride >= 3D (packed rows, or the folded table's
@@ -539,29 +539,103 @@ size_t nrms_forward_workspace_size(int64_t B, int32_t C, int32_t N, int32_t L, i
          nrms_user_encode_workspace_size(B, N, D) + align_up((size_t)B * N * 8) + align_up((size_t)B * 4);
 }
 
+size_t nrms_forward_state_size(int64_t V, int32_t D, int32_t with_folded_table) {
+  if (V < 0 || D <= 0) return 0;
+  return (with_folded_table ? align_up((size_t)V * (size_t)qkv_row_stride(D) * 4) : 0) +
+         2 * align_up(proj_x6_pack_floats() * 4) + align_up(fused_news_packed_floats() * 4) +
+         align_up(fused_user_packed_b_floats() * 4);
+}
+
 namespace {
 
-// nrms_forward / nrms_forward_timed. ev (optional, NRMS_FORWARD_STAGES + 1
-// events): recorded on the stream before each stage and after the last.
+// The weight-derived buffers of a forward: the folded table, both encoders'
+// split Q|K|V weights and both packed W_add -- carved from a caller's state
+// buffer (nrms_forward_prepare / nrms_forward_prepared) or from nrms_forward's
+// own workspace.
+struct WeightState {
+  float* table;   // [V][ld] (null: none)
+  float* pack;    // news Q|K|V (proj_x6_pack_floats)
+  float* upack;   // user Q|K|V
+  float* nwap;    // news W_add planes + the zero / NaN rows (fused_news_packed_floats)
+  float* uwap;    // user W_add (fused_user_packed_b_floats)
+};
+
+bool carve_state(void* buf, size_t bytes, int64_t V, int32_t D, bool with_table, WeightState* ws) {
+  Carve cv{static_cast<char*>(buf), buf ? bytes : 0};
+  ws->table = with_table ? cv.floats((size_t)V * (size_t)qkv_row_stride(D)) : nullptr;
+  ws->pack = cv.floats(proj_x6_pack_floats());
+  ws->upack = cv.floats(proj_x6_pack_floats());
+  ws->nwap = cv.floats(fused_news_packed_floats());
+  ws->uwap = cv.floats(fused_user_packed_b_floats());
+  return cv.ok;
+}
+
+// Everything of a forward that reads weights only, enqueued on the stream:
+// add_packs: all four packings in one launch; else, packed: the two Q|K|V
+// packs; want_table: the vocabulary projection into ws.table. nrms_forward
+// passes the launch folding of its own step along (cjob + counters: the
+// counter reset and classification half A in the pack launch; tail: half B in
+// the projection's tail); nrms_forward_prepare passes none, so nothing here
+// depends on an id.
+int32_t prepare_weights(const float* table, int64_t V, const nrms_encoder_weights_t* news_w,
+                        const nrms_encoder_weights_t* user_w, int arith, bool packed, bool add_packs,
+                        bool want_table, const WeightState& ws, int64_t ld, hipStream_t stream,
+                        const tl::ClassifyJob* cjob = nullptr, int32_t* counters = nullptr,
+                        const tl::TailJobs* tail = nullptr, bool* tail_done = nullptr) {
+  const int D = news_w->d_model;
+  const WeightRows nwr = qkv_rows(news_w), uwr = qkv_rows(user_w);
+  const bool h3 = arith == NRMS_GEMM_SPLIT_F16X3;
+  if (tail_done) *tail_done = false;
+  if (add_packs) {
+    if (int32_t st = launch_forward_pack(nwr, ws.pack, uwr, ws.upack, news_w->w_add, ws.nwap, h3, user_w->w_add,
+                                         ws.uwap, stream, cjob, counters))
+      return st;
+  } else if (packed) {
+    if (int32_t st = launch_proj_x6_pack(nwr, ws.pack, &uwr, ws.upack, h3, stream)) return st;
+  }
+  if (!want_table) return NRMS_OK;
+  return project_qkv(table, V, contiguous_rows(D), nullptr, V, news_w, ws.pack, packed, ws.table, ld, stream,
+                     nullptr, arith, tail, tail_done);
+}
+
+// nrms_forward[_timed] (state null: the weight-derived buffers are carved from
+// the workspace and prepared first, with the step's classification folded into
+// those launches) and nrms_forward_prepared[_timed] (state: they are read from
+// it, and the step starts with the classification's own two launches). ev
+// (optional, NRMS_FORWARD_STAGES + 1 events): recorded on the stream before
+// each stage and after the last.
 int32_t forward_impl(const int64_t* cand_ids, const int64_t* clicked_ids, int64_t B, int32_t C,
                      int32_t N, int32_t L, const float* table, int64_t V,
                      const nrms_encoder_weights_t* news_w, const nrms_encoder_weights_t* user_w,
                      int32_t proj_mode, float* logits, void* workspace, size_t workspace_bytes,
-                     hipStream_t stream, hipEvent_t* ev) {
+                     hipStream_t stream, hipEvent_t* ev, const nrms_forward_state_t* state, bool prepared) {
   if (B < 0 || C < 0 || N <= 0 || L <= 0 || V <= 0) return NRMS_ERR_INVALID_ARG;
   if (int32_t st = shape_ok(news_w)) return st;
   if (int32_t st = shape_ok(user_w)) return st;
   if (news_w->d_model != user_w->d_model) return NRMS_ERR_INVALID_ARG;
-  if (B == 0) return NRMS_OK;
-  if (!cand_ids || !clicked_ids || !table || !logits) return NRMS_ERR_INVALID_ARG;
   const int D = news_w->d_model;
   const int64_t n_clk = B * N, n_all = B * (C + N);
   const bool folded = use_folded(proj_mode, n_all * L, V);
+  const int arith = gemm_arith();
+  WeightState sw{};
+  if (prepared) {
+    if (!state || !state->buffer || state->V != V || state->D != D || state->gemm_arith != arith)
+      return NRMS_ERR_INVALID_ARG;
+    const bool has_table = (state->flags & NRMS_STATE_FOLDED_TABLE) != 0;
+    if (folded && !has_table) return NRMS_ERR_INVALID_ARG;
+    if (state->ld_qkv != qkv_row_stride(D)) return NRMS_ERR_INVALID_ARG;
+    if (state->bytes < nrms_forward_state_size(V, D, has_table) ||
+        !carve_state(state->buffer, state->bytes, V, D, has_table, &sw))
+      return NRMS_ERR_WORKSPACE;
+  }
+  if (B == 0) return NRMS_OK;
+  if (!cand_ids || !clicked_ids || !logits || (!table && !(prepared && folded))) return NRMS_ERR_INVALID_ARG;
+  // (the prepared folded table lives in the state: the workspace has no rows then)
   const NewsSizes z = news_sizes(n_all, L, V, D, folded);
-  const int64_t ld = news_ld(news_w, L);
+  const int64_t ld = (prepared && folded) ? state->ld_qkv : news_ld(news_w, L);
   const int64_t uld = user_ld(user_w, N);
   Carve cv{static_cast<char*>(workspace), workspace ? workspace_bytes : 0};
-  float* qkv = cv.floats(z.qkv);
+  float* qkv = (prepared && folded) ? sw.table : cv.floats(z.qkv);
   float* ctx = cv.floats(z.ctx);
   float* scores = cv.floats(z.scores);
   float* wap = cv.floats(z.wap);
@@ -583,7 +657,6 @@ int32_t forward_impl(const int64_t* cand_ids, const int64_t* clicked_ids, int64_
 
   int32_t st;
   bool deduped = false, classified = false;
-  const int arith = gemm_arith();
   const bool user_fused = fused_user_supported(N, D, user_w->n_heads, user_w->query_dim) &&
                           ((uintptr_t)user % 16) == 0;
   // with the UserEncoder's row-list projection the clicked padding titles'
@@ -592,38 +665,58 @@ int32_t forward_impl(const int64_t* cand_ids, const int64_t* clicked_ids, int64_
   const int64_t bcast_from = (user_fused && arith != NRMS_GEMM_F32) ? n_all : 0;
   // ... and the news kernel lists the UserEncoder's rows in its prologue
   const bool user_rows_here = user_fused && arith != NRMS_GEMM_F32;
-  if ((st = rec(0))) return st;
-  // every weight split / packing of the step in one launch: both encoders'
-  // Q|K|V, and (fused tails) both W_add
-  const WeightRows nwr = qkv_rows(news_w), uwr = qkv_rows(user_w);
-  const bool packed = arith != NRMS_GEMM_F32 && proj_x6_supported(D, 3 * D, nwr);
-  const bool h3 = arith == NRMS_GEMM_SPLIT_F16X3;
-  const bool all_packed = packed && folded && user_fused;   // (the fused news tail takes folded + L = 20)
+  // every weight split / packing in one launch: both encoders' Q|K|V, and
+  // (fused tails) both W_add
+  const bool packed = arith != NRMS_GEMM_F32 && proj_x6_supported(D, 3 * D, qkv_rows(news_w));
   const bool news_fused_ok = fused_news_supported(L, D, news_w->n_heads, news_w->query_dim);
-  const bool prepacked = all_packed && news_fused_ok;
-  // the titles' classification without a launch of its own (titles.hpp): the
-  // first half in the pack launch, the second in the vocabulary projection's tail
+  bool prepacked;
+  if (prepared) {
+    // (the state's packs were made under this arithmetic: the Q|K|V packs are
+    // there exactly when this step would make them)
+    if (packed != ((state->flags & NRMS_STATE_QKV_PACKS) != 0)) return NRMS_ERR_INVALID_ARG;
+    if (packed) { pack = sw.pack; upack = sw.upack; }
+    // both W_add from the state, or both packed by this step's own launches
+    // into its workspace: a step writes nothing into the state
+    prepacked = packed && user_fused && news_fused_ok && (state->flags & NRMS_STATE_ADD_PACKS) != 0;
+    if (prepacked) { uwap = sw.uwap; }
+  } else {
+    const bool all_packed = packed && folded && user_fused;   // (the fused news tail takes folded + L = 20)
+    prepacked = all_packed && news_fused_ok;
+  }
+  if ((st = rec(0))) return st;
+  // the news launch's weights (read-only when prepacked) and its own part
+  float* nwap = (prepared && prepacked) ? sw.nwap : wap;
+  float* step_ws = wap + fused_news_packed_floats();
+  // the titles' classification without the atomics (titles.hpp): the first
+  // half in the pack launch and the second in the vocabulary projection's
+  // tail, or (prepared: neither is part of the step) in two launches of its own
   tl::ClassifyJob cjob{};
   tl::TailJobs ntail{};
-  const bool split_cls =
-      g_split_classify && prepacked && fused_news_classify_split(wap, clicked_ids, n_clk, cand_ids, n_all, V, &cjob, &ntail.sc);
-  if (prepacked) {
-    if ((st = launch_forward_pack(nwr, pack, uwr, upack, news_w->w_add, wap, h3, user_w->w_add, uwap, stream,
-                                  split_cls ? &cjob : nullptr)))
-      return st;
-  } else if (packed && (st = launch_proj_x6_pack(nwr, pack, &uwr, upack, h3, stream))) {
-    return st;
+  const bool split_cls = g_split_classify && prepacked && folded &&
+                         fused_news_classify_split(step_ws, clicked_ids, n_clk, cand_ids, n_all, V, &cjob, &ntail.sc);
+  bool tail_done = false;
+  if (prepared) {
+    if (prepacked) {
+      int32_t* counters = reinterpret_cast<int32_t*>(step_ws);
+      if ((st = launch_forward_classify(split_cls ? &cjob : nullptr, counters, stream))) return st;
+      if (split_cls && !g_skip_classify_tail) {
+        if ((st = launch_forward_scatter(ntail.sc, stream))) return st;
+        tail_done = true;
+      }
+    }
+  } else {
+    const WeightState own{folded ? qkv : nullptr, pack, upack, wap, uwap};
+    st = prepare_weights(table, V, news_w, user_w, arith, packed, prepacked, folded, own, ld, stream,
+                         split_cls ? &cjob : nullptr, reinterpret_cast<int32_t*>(step_ws),
+                         (split_cls && !g_skip_classify_tail) ? &ntail : nullptr, &tail_done);
+    if (st) return st;
   }
   if (folded) {
-    bool tail_done = false;
-    st = project_qkv(table, V, contiguous_rows(D), nullptr, V, news_w, pack, packed, qkv, ld, stream, nullptr,
-                     arith, (split_cls && !g_skip_classify_tail) ? &ntail : nullptr, &tail_done);
-    if (st) return st;
     if ((st = rec(1))) return st;
-    // (without the tail the news launch classifies the titles itself)
+    // (without the second half the news launch classifies the titles itself)
     st = encode_from_qkv(qkv, ld, V, clicked_ids, n_clk, cand_ids, n_all, L, news_w, ctx, scores,
-                         news, stream, wap, &deduped, bcast_from, user_rows_here ? ulist : nullptr, n_clk,
-                         prepacked, false, &classified, split_cls && tail_done);
+                         news, stream, nwap, &deduped, bcast_from, user_rows_here ? ulist : nullptr, n_clk,
+                         prepacked, false, &classified, split_cls && tail_done, step_ws);
   } else {
     st = project_qkv(table, V, contiguous_rows(D), clicked_ids, n_clk * L, news_w, pack, packed, qkv, ld,
                      stream, nullptr, arith);
@@ -636,8 +729,8 @@ int32_t forward_impl(const int64_t* cand_ids, const int64_t* clicked_ids, int64_
     // titles' copies are written for every title, so the UserEncoder and the
     // scorer read plain rows)
     st = encode_from_qkv(qkv, ld, n_all * L, clicked_ids, n_clk, cand_ids, n_all, L, news_w, ctx,
-                         scores, news, stream, wap, nullptr, 0, nullptr, 0, false, /*direct_rows=*/true,
-                         &classified);
+                         scores, news, stream, nwap, nullptr, 0, nullptr, 0, prepacked, /*direct_rows=*/true,
+                         &classified, false, step_ws);
   }
   if (st) return st;
   if ((st = rec(2))) return st;
@@ -652,15 +745,15 @@ int32_t forward_impl(const int64_t* cand_ids, const int64_t* clicked_ids, int64_
   // (one news vector) collapse into one row carrying their count
   const bool user_compact = user_fused && classified && token_compaction() && N <= 64;
   PaddingGroups pg{nullptr, nullptr, nullptr};
-  const PaddingGroups pg_all = deduped ? fused_news_padding_groups(wap, n_all) : pg;
-  const PaddingGroups pg_flags = classified ? fused_news_padding_groups(wap, n_all) : pg;
+  const PaddingGroups pg_all = deduped ? fused_news_padding_groups(step_ws, n_all) : pg;
+  const PaddingGroups pg_flags = classified ? fused_news_padding_groups(step_ws, n_all) : pg;
   // the users' longest-first dispatch order in the projection's tail (titles.hpp)
   tl::TailJobs utail{};
   const bool order_tail = g_split_classify && user_compact && user_lpt() && B * N <= INT32_MAX;
   if (order_tail) utail.uo = tl::UserOrder{pg_flags.pad_title, uorder, B, N};
   bool order_ready = false;
   if (user_dedupe) {
-    pg = fused_news_padding_groups(wap, n_all);
+    pg = fused_news_padding_groups(step_ws, n_all);
     // (listed by the news kernel's prologue in the folded mode; the direct mode
     // has no ids to deduplicate by, so user_dedupe is false there)
     st = project_qkv(news, n_clk, contiguous_rows(D), ulist, n_clk, user_w, upack, packed, uqkv, uld, stream,
@@ -701,7 +794,73 @@ int32_t nrms_forward(const int64_t* cand_ids, const int64_t* clicked_ids, int64_
                      int32_t proj_mode, float* logits, void* workspace, size_t workspace_bytes,
                      hipStream_t stream) {
   return forward_impl(cand_ids, clicked_ids, B, C, N, L, table, V, news_w, user_w, proj_mode, logits,
-                      workspace, workspace_bytes, stream, nullptr);
+                      workspace, workspace_bytes, stream, nullptr, nullptr, false);
+}
+
+int32_t nrms_forward_prepare(const float* table, int64_t V, const nrms_encoder_weights_t* news_w,
+                             const nrms_encoder_weights_t* user_w, int32_t with_folded_table, void* state_buf,
+                             size_t state_bytes, nrms_forward_state_t* state, hipStream_t stream) {
+  if (!state) return NRMS_ERR_INVALID_ARG;
+  *state = nrms_forward_state_t{};   // (unusable until this call succeeds)
+  if (V <= 0 || !table) return NRMS_ERR_INVALID_ARG;
+  if (int32_t st = shape_ok(news_w)) return st;
+  if (int32_t st = shape_ok(user_w)) return st;
+  if (news_w->d_model != user_w->d_model) return NRMS_ERR_INVALID_ARG;
+  const int D = news_w->d_model;
+  const bool with_table = with_folded_table != 0;
+  WeightState sw{};
+  if (!state_buf || state_bytes < nrms_forward_state_size(V, D, with_table) ||
+      !carve_state(state_buf, state_bytes, V, D, with_table, &sw))
+    return NRMS_ERR_WORKSPACE;
+  const int arith = gemm_arith();
+  const bool packed = arith != NRMS_GEMM_F32 && proj_x6_supported(D, 3 * D, qkv_rows(news_w));
+  // (the W_add packs are those of the fused tails: any title length / history
+  // length they take has the same packs)
+  const bool add_packs = packed && fused_news_supported(tl::FL, D, news_w->n_heads, news_w->query_dim) &&
+                         fused_user_supported(1, D, user_w->n_heads, user_w->query_dim);
+  const int64_t ld = qkv_row_stride(D);
+  if (int32_t st = prepare_weights(table, V, news_w, user_w, arith, packed, add_packs, with_table, sw, ld, stream))
+    return st;
+  state->buffer = state_buf;
+  state->bytes = state_bytes;
+  state->V = V;
+  state->D = D;
+  state->ld_qkv = (int32_t)ld;
+  state->gemm_arith = arith;
+  state->flags = (with_table ? NRMS_STATE_FOLDED_TABLE : 0) | (packed ? NRMS_STATE_QKV_PACKS : 0) |
+                 (add_packs ? NRMS_STATE_ADD_PACKS : 0);
+  return NRMS_OK;
+}
+
+size_t nrms_forward_prepared_workspace_size(int64_t B, int32_t C, int32_t N, int32_t L, int32_t D) {
+  return nrms_forward_workspace_size(B, C, N, L, 0, D, NRMS_PROJ_DIRECT);
+}
+
+size_t nrms_forward_prepared_folded_workspace_size(int64_t B, int32_t C, int32_t N, int32_t L, int32_t D) {
+  const size_t all = nrms_forward_prepared_workspace_size(B, C, N, L, D);
+  if (all == 0) return 0;
+  return all - align_up((size_t)B * (size_t)(C + N) * (size_t)L * (size_t)qkv_row_stride(D) * 4);
+}
+
+int32_t nrms_forward_prepared(const int64_t* cand_ids, const int64_t* clicked_ids, int64_t B, int32_t C,
+                              int32_t N, int32_t L, const float* table, int64_t V,
+                              const nrms_encoder_weights_t* news_w, const nrms_encoder_weights_t* user_w,
+                              int32_t proj_mode, float* logits, void* workspace, size_t workspace_bytes,
+                              hipStream_t stream, const nrms_forward_state_t* state) {
+  return forward_impl(cand_ids, clicked_ids, B, C, N, L, table, V, news_w, user_w, proj_mode, logits,
+                      workspace, workspace_bytes, stream, nullptr, state, true);
+}
+
+int32_t nrms_forward_prepared_timed(const int64_t* cand_ids, const int64_t* clicked_ids, int64_t B, int32_t C,
+                                    int32_t N, int32_t L, const float* table, int64_t V,
+                                    const nrms_encoder_weights_t* news_w, const nrms_encoder_weights_t* user_w,
+                                    int32_t proj_mode, float* logits, void* workspace, size_t workspace_bytes,
+                                    hipStream_t stream, const nrms_forward_state_t* state,
+                                    hipEvent_t* stage_events, int32_t n_events) {
+  if (n_events != 0 && (n_events != NRMS_FORWARD_STAGES + 1 || !stage_events))
+    return NRMS_ERR_INVALID_ARG;
+  return forward_impl(cand_ids, clicked_ids, B, C, N, L, table, V, news_w, user_w, proj_mode, logits,
+                      workspace, workspace_bytes, stream, n_events ? stage_events : nullptr, state, true);
 }
 
 int32_t nrms_forward_timed(const int64_t* cand_ids, const int64_t* clicked_ids, int64_t B, int32_t C,
@@ -712,7 +871,7 @@ int32_t nrms_forward_timed(const int64_t* cand_ids, const int64_t* clicked_ids, 
   if (n_events != 0 && (n_events != NRMS_FORWARD_STAGES + 1 || !stage_events))
     return NRMS_ERR_INVALID_ARG;
   return forward_impl(cand_ids, clicked_ids, B, C, N, L, table, V, news_w, user_w, proj_mode, logits,
-                      workspace, workspace_bytes, stream, n_events ? stage_events : nullptr);
+                      workspace, workspace_bytes, stream, n_events ? stage_events : nullptr, nullptr, false);
 }
 
 const char* nrms_forward_stage_name(int32_t i) {

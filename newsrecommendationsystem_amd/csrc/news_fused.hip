@@ -1312,13 +1312,17 @@ __global__ __launch_bounds__(NTHR, 1) void fused_news_kernel(
 
 }  // namespace
 
-// Workspace after the packed W_add, special rows and f16 planes: int32
+// Workspace after the packed W_add, special rows and f16 planes -- the
+// weights' part (fused_news_packed_floats), which a launch only reads once
+// packed -- the launch's own part (step_ws: by default right behind the
+// weights' part, or anywhere else, nrms_forward_prepared): int32
 // counters [NCNT] (reset by the pack kernel of every launch), the recheck list
 // (4 per group), the bucket lists [NBK][n], the compacted rows [n][20], the
 // split classification's slot codes [n] and block counts [nblk][8] (16-B
 // aligned), then bytes: counts [n] and all-padding flags [n].
 static size_t fused_news_list_offset() { return (size_t)WAP_MAX + SPECIAL_FLOATS + WAP2_FLOATS; }
 static int64_t max_groups(int64_t n_titles) { return (n_titles + FT - 1) / FT + NBK; }
+size_t fused_news_packed_floats() { return fused_news_list_offset(); }
 size_t fused_news_workspace_floats(int64_t n_titles) {
   return fused_news_list_offset() + NCNT + 4 * (size_t)max_groups(n_titles) + (size_t)NBK * n_titles + 4 +
          (size_t)FL * n_titles + (size_t)n_titles + 4 + (size_t)tl::BLK_INTS * tl::classify_blocks(n_titles) +
@@ -1335,9 +1339,9 @@ struct NewsWs {
   uint8_t* cnt;
   uint8_t* pad_title;
 };
-NewsWs news_ws(float* ws, int64_t n_titles) {
+NewsWs news_ws(float* step_ws, int64_t n_titles) {
   NewsWs z;
-  z.counters = reinterpret_cast<int32_t*>(ws + fused_news_list_offset());
+  z.counters = reinterpret_cast<int32_t*>(step_ws);
   z.recheck = z.counters + NCNT;
   z.list = z.recheck + 4 * max_groups(n_titles);
   // (16-B aligned: the classification writes each title's 80-B row as 16-B stores)
@@ -1406,11 +1410,11 @@ ClassifyDecision classify_decision(const int64_t* ids_a, const int64_t* ids_b, i
 }
 }  // namespace
 
-bool fused_news_classify_split(float* ws, const int64_t* ids_a, int64_t n_seq_a, const int64_t* ids_b,
+bool fused_news_classify_split(float* step_ws, const int64_t* ids_a, int64_t n_seq_a, const int64_t* ids_b,
                                int64_t n_titles, int64_t n_rows, tl::ClassifyJob* job, tl::TitleScatter* sc) {
   const ClassifyDecision d = classify_decision(ids_a, ids_b, n_titles, n_rows, false, -1, -1);
-  if (!d.classify || n_titles == 0 || ((uintptr_t)ws % 16)) return false;
-  const NewsWs z = news_ws(ws, n_titles);
+  if (!d.classify || n_titles == 0 || ((uintptr_t)step_ws % 16)) return false;
+  const NewsWs z = news_ws(step_ws, n_titles);
   const int64_t nblk = tl::classify_blocks(n_titles);
   job->rm = RowMap{ids_a, ids_b, n_seq_a, n_titles, n_rows, false};
   job->tt = Titles{z.crow, z.cnt, z.pad_title, z.list, z.counters, n_titles};
@@ -1427,18 +1431,20 @@ int32_t launch_fused_news(const float* qkv, int64_t ldq, int64_t n_rows, const i
                           const float* w_add, const float* b_add, const float* q_add, float* ws,
                           float* out, hipStream_t s, int dedupe_setting, bool* deduped,
                           int64_t broadcast_from, int64_t* user_list, int64_t user_rows, bool prepacked,
-                          bool direct_rows, int compact_setting, bool* classified, bool preclassified) {
+                          bool direct_rows, int compact_setting, bool* classified, bool preclassified,
+                          float* step_ws) {
   if (deduped) *deduped = false;
   if (classified) *classified = false;
   if (n_titles == 0) return NRMS_OK;
-  if (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)ws) % 16) return NRMS_ERR_UNSUPPORTED;
+  if (!step_ws) step_ws = ws + fused_news_list_offset();
+  if (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)ws | (uintptr_t)step_ws) % 16) return NRMS_ERR_UNSUPPORTED;
   if (ldq < 3 * FD || ldq % 4) return NRMS_ERR_UNSUPPORTED;   // float4 q / k slices
   if (max_groups(n_titles) >= (1ll << 27)) return NRMS_ERR_UNSUPPORTED;   // recheck entries: group << 4 | mask
   // F16X3: f16x3 main pass, x6 recheck pass
   const int arith = gemm_arith();
   const bool h3 = arith == NRMS_GEMM_SPLIT_F16X3;
   const bool x6 = arith != NRMS_GEMM_F32;
-  const NewsWs z = news_ws(ws, n_titles);
+  const NewsWs z = news_ws(step_ws, n_titles);
   const RecheckList rl{z.counters + CNT_RECHECK, z.recheck};
   const ClassifyDecision cd =
       classify_decision(ids_a, ids_b, n_titles, n_rows, direct_rows, dedupe_setting, compact_setting);
@@ -1460,7 +1466,8 @@ int32_t launch_fused_news(const float* qkv, int64_t ldq, int64_t n_rows, const i
   const UserRows ur{dedupe && user_list && user_rows > 0 ? user_list : nullptr, user_rows, z.pad_title,
                     z.counters + CNT_REP, z.counters + CNT_USER};
   if (prepacked) {
-    // (forward_pack_kernel packed W_add and reset the counters)
+    // (forward_pack_kernel packed W_add and reset the counters; the prepared
+    // step: nrms_forward_prepare packed, forward_classify_kernel reset)
   } else if (x6) {
     const int npk = XKS * FNT * 64 * 8 + SPECIAL_FLOATS;
     if (h3)
@@ -1512,8 +1519,8 @@ int32_t launch_fused_news(const float* qkv, int64_t ldq, int64_t n_rows, const i
   return st;
 }
 
-PaddingGroups fused_news_padding_groups(float* ws, int64_t n_titles) {
-  const NewsWs z = news_ws(ws, n_titles);
+PaddingGroups fused_news_padding_groups(float* step_ws, int64_t n_titles) {
+  const NewsWs z = news_ws(step_ws, n_titles);
   return PaddingGroups{z.pad_title, z.counters + CNT_REP, z.counters + CNT_USER};
 }
 

@@ -12,6 +12,7 @@ namespace nrms {
 namespace tl {
 struct ClassifyJob;
 struct TailJobs;
+struct TitleScatter;
 }  // namespace tl
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
@@ -223,7 +224,13 @@ int32_t launch_proj_x6(const float* X, int64_t n_rows_x, ARows ar, const int64_t
 // (titles.hpp).
 int32_t launch_forward_pack(const WeightRows& wn, float* pn, const WeightRows& wu, float* pu,
                             const float* news_wadd, float* news_ws, bool f16, const float* user_wadd,
-                            float* user_ws, hipStream_t s, const tl::ClassifyJob* cls = nullptr);
+                            float* user_ws, hipStream_t s, const tl::ClassifyJob* cls = nullptr,
+                            int32_t* counters = nullptr);
+// The prepared step's first launches (proj_x6.hip): the news counters' reset
+// with half A of the split classification (cls null: the reset alone), and
+// half B (the scatter into the bucket lists).
+int32_t launch_forward_classify(const tl::ClassifyJob* cls, int32_t* counters, hipStream_t s);
+int32_t launch_forward_scatter(const tl::TitleScatter& sc, hipStream_t s);
 int32_t launch_gemm_additive_score(const float* X, int64_t M, int K, const float* W,
                                    const float* b, const float* q, int N, float* score,
                                    hipStream_t s);
@@ -329,6 +336,10 @@ int set_thread_token_compaction(int on);
 
 // workspace of launch_fused_news: packed W_add, special rows, recheck list
 size_t fused_news_workspace_floats(int64_t n_titles);
+// ... of which the weights' part comes first (packed W_add, special rows, f16
+// planes: read-only once packed); the rest is the launch's own (step_ws below:
+// counters, recheck list, bucket lists, classification arrays)
+size_t fused_news_packed_floats();
 bool fused_news_supported(int L, int D, int H, int Q);
 // dedupe_setting / compact_setting: -1 = the process-wide setting
 // (nrms_set_title_dedupe / nrms_set_token_compaction), else 0 / 1; *deduped
@@ -352,8 +363,10 @@ int32_t launch_fused_news(const float* qkv, int64_t ldq, int64_t n_rows, const i
                           float* out, hipStream_t s, int dedupe_setting = -1, bool* deduped = nullptr,
                           int64_t broadcast_from = 0, int64_t* user_list = nullptr, int64_t user_rows = 0,
                           bool prepacked = false, bool direct_rows = false, int compact_setting = -1,
-                          bool* classified = nullptr, bool preclassified = false);
-PaddingGroups fused_news_padding_groups(float* ws, int64_t n_titles);
+                          bool* classified = nullptr, bool preclassified = false, float* step_ws = nullptr);
+// step_ws: the launch's own part of the workspace (null: ws +
+// fused_news_packed_floats()), 16-B aligned
+PaddingGroups fused_news_padding_groups(float* step_ws, int64_t n_titles);
 // The rows m < n_rows of titles not copied from rep (the UserEncoder's rows to
 // project), appended to list in any order; their count in *pg.user_count.
 int32_t launch_user_row_list(const PaddingGroups& pg, int64_t n_rows, int64_t* list, hipStream_t s);

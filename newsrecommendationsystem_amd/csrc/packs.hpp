@@ -40,11 +40,16 @@ __device__ __forceinline__ void split3(float x, __bf16& hi, __bf16& mid, __bf16&
 // x6 planes [ks][nt][plane][lane][8] (bf16 hi | mid | lo of Wa[16 nt + (lane
 // & 15)][32 ks + 8 (lane >> 4) + i], 0 past Q or D); F16: also the fp16 planes
 // (2^11 hi, 2^11-scaled residual, hi) after the special rows; then the zero
-// and NaN q|k|v rows; idx < NEWS_NCOUNT resets the launch's counters.
+// and NaN q|k|v rows; idx < NEWS_NCOUNT resets the launch's counters
+// (counters null: a packing outside a step, nrms_forward_prepare -- the step
+// resets its own).
+__device__ __forceinline__ void reset_news_counters(int idx, int32_t* __restrict__ counters) {
+  if (idx < NEWS_NCOUNT) counters[idx] = idx == NEWS_CNT_REP ? INT32_MAX : 0;
+}
 template <bool F16>
 __device__ __forceinline__ void pack_news_additive(int idx, const float* __restrict__ Wa, float* __restrict__ WaP,
                                                    int32_t* __restrict__ counters) {
-  if (idx < NEWS_NCOUNT) counters[idx] = idx == NEWS_CNT_REP ? INT32_MAX : 0;
+  if (counters) reset_news_counters(idx, counters);
   if (idx >= NEWS_X6_ELEMS + NEWS_SPECIAL) return;
   if (idx >= NEWS_X6_ELEMS) {
     const int sidx = idx - NEWS_X6_ELEMS;

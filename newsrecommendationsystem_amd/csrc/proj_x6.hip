@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void forward_pack_kernel(WeightRows wn, float*
                                                            float* __restrict__ pu, const float* __restrict__ nwa,
                                                            float* __restrict__ nws, int nf16,
                                                            const float* __restrict__ uwa, float* __restrict__ uws,
-                                                           tl::ClassifyJob cj) {
+                                                           tl::ClassifyJob cj, int32_t* __restrict__ counters) {
   int b = blockIdx.x;
   const int t = threadIdx.x;
   // the classification blocks first (their id loads are the launch's long
@@ -227,7 +227,6 @@ __global__ __launch_bounds__(256) void forward_pack_kernel(WeightRows wn, float*
     b -= PACK_BLOCKS;
   }
   if (b < NEWS_ADD_BLOCKS) {
-    int32_t* counters = reinterpret_cast<int32_t*>(nws + pk::NEWS_COUNTERS);
     if (nf16) pk::pack_news_additive<true>(b * 256 + t, nwa, nws, counters);
     else pk::pack_news_additive<false>(b * 256 + t, nwa, nws, counters);
     return;
@@ -236,6 +235,19 @@ __global__ __launch_bounds__(256) void forward_pack_kernel(WeightRows wn, float*
   if (nf16) pk::pack_user_additive_h3(b, t, uwa, uws);
   else pk::pack_user_additive(b * 256 + t, uwa, uws, 1);
   static_assert(tl::CLS_T == 256, "classification blocks of the pack launch");
+}
+
+// The prepared step's (nrms_forward_prepared) replacement for the pack launch:
+// the news counters' reset and half A of the titles' classification (cj.nblk
+// blocks; none: the reset alone), then half B as a launch of its own -- the
+// vocabulary projection whose tail it rode in is not part of that step.
+__global__ __launch_bounds__(256) void forward_classify_kernel(tl::ClassifyJob cj, int32_t* __restrict__ counters) {
+  if (blockIdx.x == 0) pk::reset_news_counters(threadIdx.x, counters);
+  if (blockIdx.x < cj.nblk) tl::classify_block<true, true>(blockIdx.x, threadIdx.x, cj.rm, cj.tt, cj.dedupe, cj.compact, cj.sl);
+}
+
+__global__ __launch_bounds__(256) void forward_scatter_kernel(tl::TailJobs tj) {
+  tl::run_tail_jobs<256>(tj, threadIdx.x);
 }
 
 // SCATTER: output row m goes to Y row row_ids[m] (row-list mode; the count is
@@ -714,7 +726,7 @@ int32_t launch_proj_x6_pack(const WeightRows& w0, float* d0, const WeightRows* w
 
 int32_t launch_forward_pack(const WeightRows& wn, float* pn, const WeightRows& wu, float* pu,
                             const float* news_wadd, float* news_ws, bool f16, const float* user_wadd,
-                            float* user_ws, hipStream_t s, const tl::ClassifyJob* cls) {
+                            float* user_ws, hipStream_t s, const tl::ClassifyJob* cls, int32_t* counters) {
   if (((uintptr_t)pn | (uintptr_t)pu) % 16) return NRMS_ERR_UNSUPPORTED;
   tl::ClassifyJob cj{};
   if (cls) cj = *cls;
@@ -722,7 +734,32 @@ int32_t launch_forward_pack(const WeightRows& wn, float* pn, const WeightRows& w
                          (f16 ? pk::USER_H3_BLOCKS : USER_ADD_BLOCKS) + (cls ? cj.nblk : 0);
   if (blocks > INT32_MAX) return NRMS_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(forward_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, s, wn, pn, wu, pu, news_wadd,
-                     news_ws, f16 ? 1 : 0, user_wadd, user_ws, cj);
+                     news_ws, f16 ? 1 : 0, user_wadd, user_ws, cj, counters);
+  return launch_status();
+}
+
+int32_t launch_forward_classify(const tl::ClassifyJob* cls, int32_t* counters, hipStream_t s) {
+  tl::ClassifyJob cj{};
+  if (cls) cj = *cls;
+  if (!counters || cj.nblk > INT32_MAX) return NRMS_ERR_UNSUPPORTED;
+  const int64_t blocks = cj.nblk > 0 ? cj.nblk : 1;
+  hipLaunchKernelGGL(forward_classify_kernel, dim3((unsigned)blocks), dim3(256), 0, s, cj, counters);
+  return launch_status();
+}
+
+int32_t launch_forward_scatter(const tl::TitleScatter& sc, hipStream_t s) {
+  if (!sc.slot || sc.nblk <= 0) return NRMS_ERR_INVALID_ARG;
+  int dev = 0, n_cu = 256;
+  if (hipGetDevice(&dev) == hipSuccess) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n_cu = v;
+  }
+  // (a workgroup per classification block, at most one per CU: each takes a
+  // contiguous range of blocks)
+  const int64_t grid = sc.nblk < n_cu ? sc.nblk : n_cu;
+  tl::TailJobs tj{};
+  tj.sc = sc;
+  hipLaunchKernelGGL(forward_scatter_kernel, dim3((unsigned)grid), dim3(256), 0, s, tj);
   return launch_status();
 }
 

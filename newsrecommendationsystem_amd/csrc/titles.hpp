@@ -21,6 +21,11 @@
 //     writes the bucket totals and the rep title into the counters; the
 //     UserEncoder's dispatch order is computed in the tail of the UserEncoder's
 //     projection.
+// In nrms_forward_prepared neither host launch is part of the step (the
+// weights are packed and the vocabulary projected once, in
+// nrms_forward_prepare), so the halves run as two small launches of their own
+// (proj_x6.hip: forward_classify_kernel, which also resets the news counters,
+// and forward_scatter_kernel: the same classify_block / run_tail_jobs code).
 // The list order is then fixed (block order, ranks within blocks): a title's
 // result does not depend on the group or slot it is encoded in, so the
 // outputs are the atomic version's.
@@ -363,10 +368,10 @@ struct ClassifyJob {
 }  // namespace tl
 
 // The forward's split classification of the titles of a folded-row fused news
-// launch on workspace ws (news_fused.hip): false when launch_fused_news would
+// launch whose own workspace part is step_ws (news_fused.hip): false when launch_fused_news would
 // not classify them; else both halves' arguments. The news launch then takes
 // preclassified = true (and prepacked: the pack's counter reset comes first).
-bool fused_news_classify_split(float* ws, const int64_t* ids_a, int64_t n_seq_a, const int64_t* ids_b,
+bool fused_news_classify_split(float* step_ws, const int64_t* ids_a, int64_t n_seq_a, const int64_t* ids_b,
                                int64_t n_titles, int64_t n_rows, tl::ClassifyJob* job, tl::TitleScatter* sc);
 
 }  // namespace nrms

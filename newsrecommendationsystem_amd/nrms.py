@@ -21,6 +21,9 @@ Differences from the reference that a caller can observe:
     runs on ATen autograd (newsrecommendationsystem_amd/train.py). Dropout
     masks come from the library's counter-based generator, not torch's RNG.
 """
+import ctypes
+import os
+
 import torch
 import torch.nn as nn
 
@@ -128,7 +131,10 @@ class NewsEncoder(nn.Module):
 
     def folded_table(self):
         """Projected vocabulary [V, 3D] (E [W_Q;W_K;W_V]^T + b), cached while
-        the embedding and Q/K/V parameters are unchanged (tensor versions)."""
+        the embedding and Q/K/V parameters are unchanged (tensor versions).
+        Inside an NRMS module the cached tensor is the table of the module's
+        prepared forward state (NRMS.forward_state stores it here): one copy
+        serves both paths."""
         key = self._fold_key()
         if self._folded is not None and self._folded[0] == key:
             return self._folded[1]
@@ -228,6 +234,45 @@ class DotProductClickPredictor(nn.Module):
         return out
 
 
+def prepared_forward_enabled(config):
+    """The scoring path reads a prepared forward state (nrms_forward_prepared)
+    instead of recomputing the weight-derived data in every call: on with
+    ``config.hip_cache_folded_table`` (default) unless the environment sets
+    NRMS_FORWARD_PREPARED=0 (the A/B switch back to nrms_forward)."""
+    return bool(getattr(config, "hip_cache_folded_table", True)) and os.environ.get("NRMS_FORWARD_PREPARED", "1") != "0"
+
+
+def resolves_folded(proj_mode, n_tokens, V):
+    """nrms_forward's projection mode for a batch of n_tokens tokens."""
+    return proj_mode == N.NRMS_PROJ_FOLDED or (proj_mode == N.NRMS_PROJ_AUTO and n_tokens > V)
+
+
+class PreparedState:
+    """One nrms_forward_state_t with the device buffer behind it. ``table`` is
+    the folded Q|K|V table [V, ld] (a view of the buffer) or None."""
+
+    def __init__(self, buf):
+        self.buf = buf
+        self.st = N.ForwardState()
+        self.key = None
+        self.shape = None
+        self.table = None
+
+    def ref(self):
+        return ctypes.byref(self.st)
+
+
+class _StateCache(dict):
+    """(arithmetic, with_folded_table) -> PreparedState. Device buffers and
+    pointers of one module: a copy of the module starts with none."""
+
+    def __deepcopy__(self, memo):
+        return _StateCache()
+
+    def __reduce__(self):
+        return (_StateCache, ())
+
+
 class NRMS(nn.Module):
     """NRMS network (src/model/NRMS/__init__.py:7-84)."""
 
@@ -239,6 +284,56 @@ class NRMS(nn.Module):
         self.click_predictor = DotProductClickPredictor()
         self._ws = _Workspace()
         self._train_calls = 0
+        self._fstates = _StateCache()
+
+    def _state_key(self):
+        """Storage and version of every parameter nrms_forward_prepare reads:
+        the embedding, and both encoders' W_Q / W_K / W_V weight and bias and
+        W_add weight (HipAdam and in-place updates bump the versions)."""
+        ps = [self.news_encoder.word_embedding.weight]
+        for enc in (self.news_encoder, self.user_encoder):
+            m = enc.multihead_self_attention
+            ps += [getattr(getattr(m, n), a) for n in ("W_Q", "W_K", "W_V") for a in ("weight", "bias")]
+            ps.append(enc.additive_attention.linear.weight)
+        return tuple((p.data_ptr(), p._version) for p in ps)
+
+    def forward_state(self, with_folded_table=True):
+        """The prepared forward state (nrms_forward_prepare) for the current
+        GEMM arithmetic: one entry per (arithmetic, with_folded_table), so a
+        graph captured under another arithmetic keeps its own. A stale entry
+        (any parameter above changed) is prepared again into the same buffer,
+        without reallocation: graphs captured over it stay valid and replay
+        the new weights. The folded table is shared with
+        ``news_encoder.folded_table()``."""
+        lib = N.load()
+        ne = self.news_encoder
+        with_table = bool(with_folded_table)
+        slot = (lib.nrms_get_gemm_arith(), with_table)
+        key = self._state_key()
+        ent = self._fstates.get(slot)
+        if ent is None or ent.key != key:
+            tab = ne.table()
+            V, D = tab.shape
+            nb = lib.nrms_forward_state_size(V, D, int(with_table))
+            if ent is None or ent.shape != (V, D) or ent.buf.device != tab.device:
+                ent = self._fstates[slot] = PreparedState(torch.empty(max(nb, 256), dtype=torch.uint8,
+                                                                      device=tab.device))
+            wn, keep_n = ne.weights()
+            wu, keep_u = self.user_encoder.weights()
+            ent.key = None
+            N.call("nrms_forward_prepare", N.ptr(tab), V, ctypes.byref(wn), ctypes.byref(wu), int(with_table),
+                   N.ptr(ent.buf), ent.buf.numel(), ent.ref(), N.stream_handle(tab.device))
+            ent.key, ent.shape = key, (V, D)
+            ld = ent.st.ld_qkv
+            ent.table = ent.buf[:V * ld * 4].view(torch.float32).view(V, ld) if with_table else None
+            # other streams may read the state next (it is shared)
+            if not torch.cuda.is_current_stream_capturing():
+                torch.cuda.current_stream(tab.device).synchronize()
+            if with_table:
+                ne._folded = None
+        if with_table and (ne._folded is None or ne._folded[1] is not ent.table):
+            ne._folded = (ne._fold_key(), ent.table)
+        return ent
 
     def forward(self, candidate_news, clicked_news):
         """candidate_news: list (1+K) of {"title": LongTensor[B, L]};
@@ -273,7 +368,19 @@ class NRMS(nn.Module):
         mode = getattr(self.config, "hip_proj_mode", N.NRMS_PROJ_AUTO) if proj_mode is None else proj_mode
         wn, keep_n = ne.weights()
         wu, keep_u = self.user_encoder.weights()
-        nb = N.load().nrms_forward_workspace_size(B, C, n_clicked, L, V, D, mode)
+        lib = N.load()
+        if prepared_forward_enabled(self.config):
+            # the weight-derived state is prepared once per parameter version;
+            # the call runs everything that reads an id
+            folded = resolves_folded(mode, B * (C + n_clicked) * L, V)
+            state = self.forward_state(folded)
+            size = lib.nrms_forward_prepared_folded_workspace_size if folded else lib.nrms_forward_prepared_workspace_size
+            ws = self._ws.get(size(B, C, n_clicked, L, D), tab.device)
+            N.call("nrms_forward_prepared", N.ptr(cand), N.ptr(clk), B, C, n_clicked, L, N.ptr(tab), V,
+                   ctypes_byref(wn), ctypes_byref(wu), mode, N.ptr(logits), N.ptr(ws), ws.numel(),
+                   N.stream_handle(tab.device), state.ref())
+            return logits
+        nb = lib.nrms_forward_workspace_size(B, C, n_clicked, L, V, D, mode)
         ws = self._ws.get(nb, tab.device)
         N.call("nrms_forward", N.ptr(cand), N.ptr(clk), B, C, n_clicked, L, N.ptr(tab), V,
                ctypes_byref(wn), ctypes_byref(wu), mode, N.ptr(logits), N.ptr(ws), ws.numel(),
@@ -281,7 +388,11 @@ class NRMS(nn.Module):
         return logits
 
     def get_news_vector(self, news):
-        return self.news_encoder(news)
+        ne = self.news_encoder
+        if (not self.training and ne.word_embedding.weight.is_cuda and prepared_forward_enabled(self.config)
+                and getattr(self.config, "hip_proj_mode", N.NRMS_PROJ_AUTO) != N.NRMS_PROJ_DIRECT):
+            self.forward_state(True)   # the encoder's cached folded table is this state's: one copy
+        return ne(news)
 
     def get_user_vector(self, clicked_news_vector):
         return self.user_encoder(clicked_news_vector)

@@ -160,9 +160,18 @@ class ForwardPlan:
         urows, urows_sq = (n_clk, B * Nc * Nc) if user_rows is None else user_rows
         att_flop = lambda seqs, l: seqs * H * 2 * (2 * l * l * dk)
         qkv_m = V if self.folded else n_all * L
+        from .nrms import prepared_forward_enabled
+        if self.folded and self.fused and prepared_forward_enabled(self.model.config):
+            # the product path's stage with a prepared state (nrms_forward_prepared:
+            # the vocabulary projection is not part of the step): the titles'
+            # classification -- the ids read; per title the compacted rows (crow,
+            # L int32), slot code, bucket-list entry, count and all-padding flag written
+            qkv_news = dict(flop=0, bytes=n_all * (8 * L + 4 * L + 4 + 4 + 2))
+        else:
+            qkv_news = dict(flop=2 * qkv_m * D * 3 * D, split=dict(gemm=2 * qkv_m * D * 3 * D),
+                            bytes=4 * (qkv_m * D + qkv_m * 3 * D + 3 * D * D))
         return {
-            "qkv_news": dict(flop=2 * qkv_m * D * 3 * D, split=dict(gemm=2 * qkv_m * D * 3 * D),
-                             bytes=4 * (qkv_m * D + qkv_m * 3 * D + 3 * D * D)),
+            "qkv_news": qkv_news,
             # gathered q|k|v rows + ids + context rows written
             "mhsa_news": dict(flop=att_flop(n_all, L),
                               bytes=n_all * L * (4 * 3 * D + (8 if self.folded else 0) + 4 * D)),
@@ -197,17 +206,37 @@ class TimedForward:
     workspace; event i is recorded on the launch stream before stage i
     (stages = nrms_forward_stage_name) and the last after the final stage.
     Unlike ForwardPlan it takes nrms_forward's internal shortcuts (the
-    UserEncoder's row-list projection after padding-title dedupe)."""
+    UserEncoder's row-list projection after padding-title dedupe).
+
+    With ``config.hip_cache_folded_table`` (default; NRMS_FORWARD_PREPARED=0
+    in the environment turns it off) the step is nrms_forward_prepared_timed
+    over the model's prepared forward state (NRMS.forward_state): the weight
+    packs and the folded table are made once per parameter version, and the
+    step runs everything that reads an id. ``run`` checks the parameters'
+    versions and prepares again, into the same buffers, when they changed; it
+    never allocates. The one semantic change: a captured graph replays the
+    prepared state, so after an in-place parameter update call ``run()`` or
+    ``refresh()`` once before replaying (the capture itself stays valid)."""
 
     def __init__(self, model, B, C, n_clicked, L, proj_mode=N.NRMS_PROJ_FOLDED):
+        from .nrms import prepared_forward_enabled, resolves_folded
         ne = model.news_encoder
+        self.model = model
         self.dev = ne.word_embedding.weight.device
         self.table = ne.table()
         self.V, self.D = self.table.shape
         self.B, self.C, self.N, self.L, self.mode = B, C, n_clicked, L, proj_mode
         lib = N.load()
-        nb = lib.nrms_forward_workspace_size(B, C, n_clicked, L, self.V, self.D, proj_mode)
-        self.ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
+        self.prepared = prepared_forward_enabled(model.config)
+        self.folded = resolves_folded(proj_mode, B * (C + n_clicked) * L, self.V)
+        if self.prepared:
+            self.state = model.forward_state(self.folded)
+            size = (lib.nrms_forward_prepared_folded_workspace_size if self.folded
+                    else lib.nrms_forward_prepared_workspace_size)
+            nb = size(B, C, n_clicked, L, self.D)
+        else:
+            nb = lib.nrms_forward_workspace_size(B, C, n_clicked, L, self.V, self.D, proj_mode)
+        self.ws = torch.empty(max(nb, 256), dtype=torch.uint8, device=self.dev)
         self.logits = torch.empty(B, C, dtype=torch.float32, device=self.dev)
         self.wn, self._keep_n = ne.weights()
         self.wu, self._keep_u = model.user_encoder.weights()
@@ -223,10 +252,23 @@ class TimedForward:
         torch.cuda.synchronize(self.dev)
         return evs
 
+    def refresh(self):
+        """Prepare the state again if a parameter changed since it was made
+        (in place: captured graphs keep reading the same buffers)."""
+        if self.prepared:
+            self.state = self.model.forward_state(self.folded)
+
     def run(self, cand_ids, clicked_ids, events=None):
         arr = None
         if events is not None:
             arr = (ctypes.c_void_p * len(events))(*[ctypes.c_void_p(e.cuda_event) for e in events])
+        if self.prepared:
+            self.refresh()
+            N.call("nrms_forward_prepared_timed", N.ptr(cand_ids), N.ptr(clicked_ids), self.B, self.C, self.N,
+                   self.L, N.ptr(self.table), self.V, ctypes.byref(self.wn), ctypes.byref(self.wu),
+                   self.mode, N.ptr(self.logits), N.ptr(self.ws), self.ws.numel(),
+                   N.stream_handle(self.dev), self.state.ref(), arr, len(events) if events is not None else 0)
+            return self.logits
         N.call("nrms_forward_timed", N.ptr(cand_ids), N.ptr(clicked_ids), self.B, self.C, self.N,
                self.L, N.ptr(self.table), self.V, ctypes.byref(self.wn), ctypes.byref(self.wu),
                self.mode, N.ptr(self.logits), N.ptr(self.ws), self.ws.numel(),
