@@ -66,7 +66,9 @@ extern "C" {
  *    ABI 9, added later (additive, no bump): nrms_forward_state_t,
  *    nrms_forward_state_size, nrms_forward_prepare,
  *    nrms_forward_prepared_workspace_size (and _folded_), nrms_forward_prepared
- *    and nrms_forward_prepared_timed. */
+ *    and nrms_forward_prepared_timed.
+ *    ABI 9, added later (additive, no bump): nrms_rank_impressions, and the
+ *    host readers nrms_behaviors_scan_any / nrms_behaviors_parse_any. */
 #define NRMS_ABI_VERSION 9
 
 typedef enum {
@@ -383,6 +385,57 @@ int32_t nrms_impression_metrics(const float* scores, const int32_t* labels,
                                 const int64_t* offsets, int64_t n_imp, double* out,
                                 hipStream_t stream);
 
+/* (ABI 9, added later) Scores and ranks of ragged impressions in one launch:
+ * what a MIND prediction file lists. Impression i owns the candidates
+ * k in [offsets[i], offsets[i+1]) (rows news_idx[k] of the news table) and
+ * the user row imp_user[i]; offsets is non-decreasing and starts at 0.
+ *   - Scores. out_score[k] is bitwise what nrms_score_pairs writes for the
+ *     pair (news_idx[k], imp_user[i]): both kernels run one shared per-wave
+ *     dot (lane-strided float4 FMAs when D % 4 == 0, scalar FMAs otherwise,
+ *     then an xor-tree sum), NaN for a candidate row or user row out of
+ *     range included. Any D >= 1; rows 16-byte aligned when D % 4 == 0, as
+ *     for nrms_score_pairs. The impression's user vector is read once and
+ *     held in registers (D % 4 == 0, its first 1024 floats; the scalar path
+ *     re-reads it through the caches).
+ *   - Ranks are 1-based, over a total order on the fp32 scores: numbers
+ *     compare by value (-0 == +0), NaN ranks above +inf, all NaNs are equal.
+ *       tie_mode NRMS_RANK_ORDER (0): rank_c = 1 + #{j : s_j > s_c or
+ *         (s_j == s_c and j > c)}, j over the same impression: the position
+ *         of c in np.argsort(s, kind="stable")[::-1], the order
+ *         nrms_impression_metrics uses; always a permutation of 1..n.
+ *         [0.5, nan, 0.5, -0.0, 0.0, inf, nan, -inf] orders as 6 1 5 2 0 4 3 7.
+ *       tie_mode NRMS_RANK_SHARED (1): rank_c = 1 + #{j : s_j > s_c}; for
+ *         finite scores the reference's value2rank (src/evaluate.py:45-48),
+ *         sorted(values, reverse=True).index(x) + 1.
+ *   - Any impression length is ranked correctly; an empty one writes nothing.
+ *     Up to NRMS_RANK_LDS_CANDIDATES candidates the impression's order keys
+ *     stay in LDS between scoring and counting. A longer impression takes a
+ *     chunked path: its workgroup re-reads the out_score values it wrote
+ *     (after a workgroup barrier), NRMS_RANK_LDS_CANDIDATES keys at a time,
+ *     and accumulates each chunk's counts in out_rank. Either way ranking
+ *     costs n^2 compares per impression, n^2 / 256 per thread; the chunked
+ *     path adds n / NRMS_RANK_LDS_CANDIDATES passes over the impression's
+ *     out_score and out_rank.
+ *   - An impression's outputs depend only on its own candidates and user row,
+ *     bit for bit: not on n_imp, on its neighbours or on the grid (one
+ *     workgroup per impression; NRMS_RANK_WAVES = 1, 2 or 4 in the
+ *     environment, read once, sets its size for measurements and changes no
+ *     output).
+ *   - Any other tie_mode, a null pointer with n_imp > 0, a negative size or
+ *     D < 1: NRMS_ERR_INVALID_ARG, checked before anything else.
+ *     n_imp == 0 is a successful no-op; n_imp >= 2^31: NRMS_ERR_UNSUPPORTED.
+ *   - No allocation, no synchronisation, no atomics; capturable into a
+ *     hipGraph. A launch failure returns NRMS_ERR_HIP. */
+#define NRMS_RANK_LDS_CANDIDATES 2048
+typedef enum {
+  NRMS_RANK_ORDER = 0,
+  NRMS_RANK_SHARED = 1
+} nrms_rank_ties_t;
+int32_t nrms_rank_impressions(const float* news, int64_t n_news, const float* user, int64_t n_users,
+                              const int64_t* news_idx, const int64_t* imp_user, const int64_t* offsets,
+                              int64_t n_imp, int32_t D, int32_t tie_mode, float* out_score,
+                              int32_t* out_rank, hipStream_t stream);
+
 /* NRMS.forward (src/model/NRMS/__init__.py:19-48), eval mode:
  * cand_ids[B, C, L], clicked_ids[B, N, L] -> logits[B, C]. Every one of the
  * B*(C+N) titles gets its news vector (forward semantics), then the user
@@ -610,6 +663,15 @@ int32_t nrms_behaviors_scan(const char* buf, int64_t len, int64_t* counts);
 int32_t nrms_behaviors_parse(const char* buf, int64_t len, const int64_t* capacity, int64_t* counts,
                              int64_t* fields, int64_t* cand_num, int32_t* labels, int64_t* cand_count,
                              int64_t* hist_num, int64_t* hist_count, int64_t* hist_user);
+/* (ABI 9, added later) The same pair for splits with or without labels (MIND's
+ * test split lists "N1 N2 N3"): each candidate token is "N<id>-<label>" or
+ * "N<id>", and a token without a label gets label -1. Same signatures,
+ * outputs and rejection rules otherwise; the scan bounds the candidates by
+ * the tokens of each line's impressions column, not by the '-' bytes. */
+int32_t nrms_behaviors_scan_any(const char* buf, int64_t len, int64_t* counts);
+int32_t nrms_behaviors_parse_any(const char* buf, int64_t len, const int64_t* capacity, int64_t* counts,
+                                 int64_t* fields, int64_t* cand_num, int32_t* labels, int64_t* cand_count,
+                                 int64_t* hist_num, int64_t* hist_count, int64_t* hist_user);
 /* news_parsed.tsv: a header naming "id" and "title" columns, then rows whose
  * id is N<digits> and whose title is a list literal of exactly L ints
  * ("[12, 7, 0, ...]"). Writes *n_rows, and for the first `capacity` rows the

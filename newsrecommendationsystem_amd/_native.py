@@ -81,6 +81,7 @@ SIGNATURES = {
     "nrms_score": (_i32, [_p, _i64, _i32, _i64, _i64, _p, _i64, _i32, _p, _p]),
     "nrms_score_pairs": (_i32, [_p, _i64, _p, _i64, _p, _p, _i64, _i32, _p, _p]),
     "nrms_impression_metrics": (_i32, [_p, _p, _p, _i64, _p, _p]),
+    "nrms_rank_impressions": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p]),
     "nrms_recommend_topk_workspace_size": (_sz, [_i64, _i64, _i32, _i32, _i32]),
     "nrms_recommend_topk": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _p, _p, _p, _sz, _p]),
     # training kernels
@@ -116,8 +117,12 @@ SIGNATURES = {
     # host-side readers (HOST pointers)
     "nrms_behaviors_scan": (_i32, [_p, _i64, _p]),
     "nrms_behaviors_parse": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "nrms_behaviors_scan_any": (_i32, [_p, _i64, _p]),
+    "nrms_behaviors_parse_any": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "nrms_news_parse": (_i32, [_p, _i64, _i32, _p, _p, _p, _p, _i64]),
 }
+NRMS_RANK_ORDER, NRMS_RANK_SHARED = 0, 1
+NRMS_RANK_LDS_CANDIDATES = 2048
 NRMS_FORWARD_STAGES = 5
 
 _lib = None

@@ -522,6 +522,18 @@ int32_t nrms_recommend_topk(const float* news, int64_t n_news, const float* user
                      workspace_bytes, stream);
 }
 
+int32_t nrms_rank_impressions(const float* news, int64_t n_news, const float* user, int64_t n_users,
+                              const int64_t* news_idx, const int64_t* imp_user, const int64_t* offsets,
+                              int64_t n_imp, int32_t D, int32_t tie_mode, float* out_score,
+                              int32_t* out_rank, hipStream_t stream) {
+  if (n_imp < 0 || n_news < 0 || n_users < 0 || D <= 0) return NRMS_ERR_INVALID_ARG;
+  if (tie_mode != NRMS_RANK_ORDER && tie_mode != NRMS_RANK_SHARED) return NRMS_ERR_INVALID_ARG;
+  if (n_imp > 0 && (!news || !user || !news_idx || !imp_user || !offsets || !out_score || !out_rank))
+    return NRMS_ERR_INVALID_ARG;
+  return launch_rank_impressions(news, n_news, user, n_users, news_idx, imp_user, offsets, n_imp, D,
+                                 tie_mode, out_score, out_rank, stream);
+}
+
 int32_t nrms_impression_metrics(const float* scores, const int32_t* labels,
                                 const int64_t* offsets, int64_t n_imp, double* out,
                                 hipStream_t stream) {

@@ -3,6 +3,9 @@
 //    vectors (evaluate.py:251-260: get_prediction per impression), one wave
 //    per (candidate, user) pair — every impression of a split in one launch
 //    instead of a Python loop with a device->host sync per impression;
+//  * the same scores with every candidate's rank inside its impression, one
+//    workgroup per impression (nrms_rank_impressions: the reference's unused
+//    value2rank, evaluate.py:45-48, for MIND prediction files);
 //  * per-impression ranking metrics (evaluate.py:24-42,160-168): AUC (the
 //    Mann-Whitney statistic with ties counted 1/2, which is what
 //    sklearn.metrics.roc_auc_score computes for binary labels), MRR, nDCG@5,
@@ -34,22 +37,109 @@ __global__ __launch_bounds__(kThreads) void score_pairs_kernel(
   }
   const float* nv = news + a * D;
   const float* uv = user + b * D;
-  float acc = 0.f;
-  if ((D & 3) == 0) {
-    const float4* n4 = reinterpret_cast<const float4*>(nv);
-    const float4* u4 = reinterpret_cast<const float4*>(uv);
-    for (int i = lane; i < D / 4; i += kWave) {
-      const float4 x = n4[i], y = u4[i];
-      acc = fmaf(x.x, y.x, acc);
-      acc = fmaf(x.y, y.y, acc);
-      acc = fmaf(x.z, y.z, acc);
-      acc = fmaf(x.w, y.w, acc);
-    }
-  } else {
-    for (int i = lane; i < D; i += kWave) acc = fmaf(nv[i], uv[i], acc);
-  }
-  acc = wave_sum(acc);
+  const UserRegs none{};
+  const float acc = (D & 3) == 0 ? wave_dot<true, false>(nv, uv, D, lane, none)
+                                 : wave_dot<false, false>(nv, uv, D, lane, none);
   if (lane == 0) out[k] = acc;
+}
+
+// ---------------------------------------------------------------------------
+// Fused per-impression score + rank (nrms_rank_impressions): one workgroup per
+// impression. Its waves (four; NRMS_RANK_WAVES for measurements, see
+// profiles/predict_bench.txt) stride over the candidates, each candidate one
+// wave_dot against the impression's user vector (held in registers: the
+// lane's float4s are loaded once), and lane 0 writes the score and, while the
+// impression fits kRankLds, its order key into LDS. After one barrier thread t
+// ranks candidates t, t + 256, ... by counting over the keys: a uniform loop of
+// broadcast 16-byte LDS reads, four VALU per key.
+//
+// An impression of more than kRankLds candidates takes the chunked path:
+// the keys are rebuilt from the out_score values this workgroup wrote
+// (workgroup barrier in between), kRankLds at a time through the same LDS
+// array, and every thread adds each chunk's count to its candidates'
+// out_rank, which it alone reads and writes. n^2 / 256 compares per thread as
+// on the fast path, plus n / kRankLds re-reads of out_score and out_rank.
+//
+// Order key: the order-preserving bit flip of the fp32 score with -0 folded
+// into +0 and every NaN mapped to the top, 0xffffffff, above +inf. No key is 0
+// (-inf gives 0x007fffff), so key_j >= key_c is key_j > key_c - 1.
+constexpr int kRankLds = NRMS_RANK_LDS_CANDIDATES;
+
+__device__ __forceinline__ uint32_t rank_key(float s) {
+  uint32_t b = __float_as_uint(s);
+  if (s != s) return 0xffffffffu;
+  if (b == 0x80000000u) b = 0u;
+  return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
+}
+
+// #{j < m : key[j] > kc, or key[j] == kc and j > cr and ties by order}; key is
+// 16-B aligned, cr (the candidate's own position relative to key[0]) may lie
+// outside [0, m).
+__device__ __forceinline__ int count_above(const uint32_t* __restrict__ key, int m, int64_t cr, uint32_t kc,
+                                           bool order) {
+  const uint32_t kge = kc - (order ? 1u : 0u);
+  int cnt = 0, j = 0;
+  for (; j + 4 <= m; j += 4) {
+    const uint4 k4 = *reinterpret_cast<const uint4*>(key + j);
+    cnt += k4.x > (j > cr ? kge : kc);
+    cnt += k4.y > (j + 1 > cr ? kge : kc);
+    cnt += k4.z > (j + 2 > cr ? kge : kc);
+    cnt += k4.w > (j + 3 > cr ? kge : kc);
+  }
+  for (; j < m; ++j) cnt += key[j] > (j > cr ? kge : kc);
+  return cnt;
+}
+
+template <bool VEC, int THREADS>
+__global__ __launch_bounds__(THREADS) void rank_impressions_kernel(
+    const float* __restrict__ news, int64_t n_news, const float* __restrict__ user, int64_t n_users,
+    const int64_t* __restrict__ news_idx, const int64_t* __restrict__ imp_user,
+    const int64_t* __restrict__ offsets, int D, int tie_mode, float* out_score, int32_t* out_rank) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_key[kRankLds];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t imp = blockIdx.x;
+  const int64_t b = offsets[imp];
+  const int64_t n = offsets[imp + 1] - b;
+  if (n <= 0) return;
+  const int64_t u = imp_user[imp];
+  const bool u_ok = (uint64_t)u < (uint64_t)n_users;
+  const float* uv = user + (u_ok ? u : 0) * D;
+  UserRegs ur{};
+  if (VEC && u_ok) ur = load_user_regs(uv, D, lane);
+  const bool in_lds = n <= kRankLds;
+  float* sc = out_score + b;
+  int32_t* rk = out_rank + b;
+
+  int64_t a = news_idx[b + (wave < n ? wave : 0)];
+  for (int64_t c = wave; c < n; c += THREADS / kWave) {
+    const int64_t cn = c + THREADS / kWave;
+    const int64_t a_next = news_idx[b + (cn < n ? cn : c)];   // the next row's index, ahead of this dot
+    float s = qnan();
+    if (u_ok && (uint64_t)a < (uint64_t)n_news) s = wave_dot<VEC, true>(news + a * D, uv, D, lane, ur);
+    if (lane == 0) {
+      sc[c] = s;
+      if (in_lds) s_key[c] = rank_key(s);
+    }
+    a = a_next;
+  }
+  __syncthreads();   // (workgroup scope: the scores written above are visible to every wave below)
+
+  const bool order = tie_mode == NRMS_RANK_ORDER;
+  if (in_lds) {
+    const int m = (int)n;
+    for (int c = tid; c < m; c += THREADS) rk[c] = 1 + count_above(s_key, m, c, s_key[c], order);
+    return;
+  }
+  for (int64_t j0 = 0; j0 < n; j0 += kRankLds) {
+    const int m = n - j0 < kRankLds ? (int)(n - j0) : kRankLds;
+    if (j0) __syncthreads();   // the previous chunk's readers are done
+    for (int j = tid; j < m; j += THREADS) s_key[j] = rank_key(sc[j0 + j]);
+    __syncthreads();
+    for (int64_t c = tid; c < n; c += THREADS) {
+      const int cnt = count_above(s_key, m, c - j0, rank_key(sc[c]), order);
+      rk[c] = (j0 ? rk[c] : 1) + cnt;
+    }
+  }
 }
 
 __device__ __forceinline__ double wave_sum_d(double v) {
@@ -136,6 +226,36 @@ int32_t launch_score_pairs(const float* news, int64_t n_news, const float* user,
   if (blocks > INT32_MAX) return NRMS_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(score_pairs_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s, news,
                      n_news, user, n_users, news_idx, user_idx, n_pairs, D, out);
+  return launch_status();
+}
+
+// NRMS_RANK_WAVES in the environment (measurement only, read once): waves per
+// impression's workgroup, 1, 2 or 4 (default). The outputs do not depend on it.
+int rank_waves_knob() {
+  static const int knob = [] {
+    const char* e = env_knob("NRMS_RANK_WAVES");
+    return e ? atoi(e) : 4;
+  }();
+  return knob;
+}
+
+int32_t launch_rank_impressions(const float* news, int64_t n_news, const float* user, int64_t n_users,
+                                const int64_t* news_idx, const int64_t* imp_user, const int64_t* offsets,
+                                int64_t n_imp, int D, int tie_mode, float* out_score, int32_t* out_rank,
+                                hipStream_t s) {
+  if (n_imp == 0) return NRMS_OK;
+  if (n_imp > INT32_MAX) return NRMS_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)n_imp);
+  const bool vec = (D & 3) == 0;
+#define NRMS_RANK_LAUNCH(V, T)                                                                          \
+  hipLaunchKernelGGL((rank_impressions_kernel<V, T>), grid, dim3(T), 0, s, news, n_news, user, n_users, \
+                     news_idx, imp_user, offsets, D, tie_mode, out_score, out_rank)
+  switch (rank_waves_knob()) {
+    case 1: if (vec) NRMS_RANK_LAUNCH(true, 64); else NRMS_RANK_LAUNCH(false, 64); break;
+    case 2: if (vec) NRMS_RANK_LAUNCH(true, 128); else NRMS_RANK_LAUNCH(false, 128); break;
+    default: if (vec) NRMS_RANK_LAUNCH(true, 256); else NRMS_RANK_LAUNCH(false, 256); break;
+  }
+#undef NRMS_RANK_LAUNCH
   return launch_status();
 }
 

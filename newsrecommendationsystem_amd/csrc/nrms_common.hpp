@@ -64,6 +64,60 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// The eval scorers' dot of one news row with one user row, one wave per pair
+// (score_pairs_kernel and rank_impressions_kernel, eval.hip: bitwise the same
+// score in both). D % 4 == 0 (VEC, rows 16-B aligned): lane l takes the
+// float4s l, l + 64, ... with four FMAs each, x to w; otherwise the floats
+// l, l + 64, ...; then the xor-tree wave_sum. The bits depend on the values
+// and on D alone, not on where the user's floats are read from: a caller that
+// scores one user against many rows loads the lane's first kDotUserRegs
+// float4s once (load_user_regs) and passes them in, further ones (D > 1024)
+// are read from memory each time.
+constexpr int kDotUserRegs = 4;
+struct UserRegs {
+  float4 v[kDotUserRegs];
+};
+__device__ __forceinline__ float fma4(const float4 x, const float4 y, float acc) {
+  acc = fmaf(x.x, y.x, acc);
+  acc = fmaf(x.y, y.y, acc);
+  acc = fmaf(x.z, y.z, acc);
+  acc = fmaf(x.w, y.w, acc);
+  return acc;
+}
+__device__ __forceinline__ UserRegs load_user_regs(const float* __restrict__ uv, int D, int lane) {
+  UserRegs ur;
+  const float4* u4 = reinterpret_cast<const float4*>(uv);
+#pragma unroll
+  for (int r = 0; r < kDotUserRegs; ++r) {
+    const int i = lane + r * kWave;
+    ur.v[r] = i < D / 4 ? u4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  return ur;
+}
+template <bool VEC, bool CACHED>
+__device__ __forceinline__ float wave_dot(const float* __restrict__ nv, const float* __restrict__ uv, int D,
+                                          int lane, const UserRegs& ur) {
+  float acc = 0.f;
+  if constexpr (VEC) {
+    const float4* n4 = reinterpret_cast<const float4*>(nv);
+    const float4* u4 = reinterpret_cast<const float4*>(uv);
+    int i = lane;
+    if constexpr (CACHED) {
+#pragma unroll
+      for (int r = 0; r < kDotUserRegs; ++r) {
+        if (i < D / 4) {
+          acc = fma4(n4[i], ur.v[r], acc);
+          i += kWave;
+        }
+      }
+    }
+    for (; i < D / 4; i += kWave) acc = fma4(n4[i], u4[i], acc);
+  } else {
+    for (int i = lane; i < D; i += kWave) acc = fmaf(nv[i], uv[i], acc);
+  }
+  return wave_sum(acc);
+}
+
 // max that propagates NaN (torch.max semantics): any NaN lane -> NaN.
 __device__ __forceinline__ float nan_max(float a, float b) {
   return (a != a || b != b) ? qnan() : fmaxf(a, b);
@@ -383,6 +437,12 @@ int32_t launch_topk(const float* news, int64_t n_news, const float* user, int64_
 int32_t launch_impression_metrics(const float* scores, const int32_t* labels,
                                   const int64_t* offsets, int64_t n_imp, double* out,
                                   hipStream_t s);
+// Fused per-impression score + rank (eval.hip); the contract is
+// nrms_rank_impressions' (nrms_hip.h).
+int32_t launch_rank_impressions(const float* news, int64_t n_news, const float* user, int64_t n_users,
+                                const int64_t* news_idx, const int64_t* imp_user, const int64_t* offsets,
+                                int64_t n_imp, int D, int tie_mode, float* out_score, int32_t* out_rank,
+                                hipStream_t s);
 // pg (optional): candidates that are copied all-padding titles read the rep
 // title's vector; the candidates are titles title0 + b C + c of a contiguous array
 // (news points at title0's row).

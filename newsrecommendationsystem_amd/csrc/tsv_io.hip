@@ -107,23 +107,31 @@ void for_each_line(const char* buf, int64_t len, F&& f) {
   }
 }
 
-// impressions cell "N<id>-<label> N<id>-<label> ...": tokens, or -1
+// impressions cell "N<id>-<label> N<id>-<label> ...": tokens, or -1.
+// any_form: a token may also be a bare "N<id>" (an unlabelled split), label -1.
 template <typename Emit>
-int64_t parse_impressions(const char* p, const char* e, Emit&& emit) {
+int64_t parse_impressions(const char* p, const char* e, bool any_form, Emit&& emit) {
   if (p == e) return -1;
   int64_t n = 0;
   while (true) {
     const char* q;
     const int64_t id = parse_nid(p, e, &q);
-    if (id < 0 || q >= e || *q != '-') return -1;
-    p = q + 1;
-    const char* d0 = p;
-    int64_t lab = 0;
-    while (p < e && is_digit(*p)) {
-      lab = lab * 10 + (*p - '0');
-      ++p;
+    if (id < 0) return -1;
+    int64_t lab = -1;
+    if (q < e && *q == '-') {
+      p = q + 1;
+      const char* d0 = p;
+      lab = 0;
+      while (p < e && is_digit(*p)) {
+        lab = lab * 10 + (*p - '0');
+        ++p;
+      }
+      if (p == d0 || p - d0 > 9) return -1;
+    } else if (any_form && (q == e || *q == ' ')) {
+      p = q;
+    } else {
+      return -1;
     }
-    if (p == d0 || p - d0 > 9) return -1;
     emit(id, (int32_t)lab);
     ++n;
     if (p == e) return n;
@@ -157,20 +165,33 @@ int64_t parse_history(const char* p, const char* e, Emit&& emit) {
 
 using namespace nrms;
 
-int32_t nrms_behaviors_scan(const char* buf, int64_t len, int64_t* counts) {
+namespace {
+
+// any_form: the candidates' bound is the token count of each line's
+// impressions column (its spaces + 1), since a bare "N<id>" token holds no '-'.
+int32_t behaviors_scan(const char* buf, int64_t len, int64_t* counts, bool any_form) {
   if (len < 0 || (len > 0 && !buf) || !counts) return NRMS_ERR_INVALID_ARG;
   // upper bounds: a line per '\n' (+ 1), a candidate token per '-', an id per 'N'
   int64_t nl, dash, nn;
   if (!scan_bytes(buf, len, &nl, &dash, &nn)) return NRMS_ERR_UNSUPPORTED;
+  if (any_form) {
+    dash = 0;
+    for_each_line(buf, len, [&](const char* p, const char* e) {
+      const Line ln = split_line(p, e);
+      if (ln.n < 5 || ln.f[4] == ln.g[4]) return;
+      ++dash;
+      for (const char* c = ln.f[4]; c < ln.g[4]; ++c) dash += *c == ' ';
+    });
+  }
   counts[0] = nl + 1;
   counts[1] = dash;
   counts[2] = nn;
   return NRMS_OK;
 }
 
-int32_t nrms_behaviors_parse(const char* buf, int64_t len, const int64_t* capacity, int64_t* counts,
-                             int64_t* fields, int64_t* cand_num, int32_t* labels, int64_t* cand_count,
-                             int64_t* hist_num, int64_t* hist_count, int64_t* hist_user) {
+int32_t behaviors_parse(const char* buf, int64_t len, const int64_t* capacity, int64_t* counts,
+                        int64_t* fields, int64_t* cand_num, int32_t* labels, int64_t* cand_count,
+                        int64_t* hist_num, int64_t* hist_count, int64_t* hist_user, bool any_form) {
   if (len < 0 || (len > 0 && !buf) || !capacity || !counts) return NRMS_ERR_INVALID_ARG;
   const int64_t cap_lines = capacity[0], cap_cand = capacity[1], cap_hist = capacity[2];
   if (cap_lines < 0 || cap_cand < 0 || cap_hist < 0) return NRMS_ERR_INVALID_ARG;
@@ -197,7 +218,7 @@ int32_t nrms_behaviors_parse(const char* buf, int64_t len, const int64_t* capaci
       fields[10 * k + 2 * c] = ln.f[c] - buf;
       fields[10 * k + 2 * c + 1] = ln.g[c] - buf;
     }
-    const int64_t c = parse_impressions(ln.f[4], ln.g[4], [&](int64_t id, int32_t lab) {
+    const int64_t c = parse_impressions(ln.f[4], ln.g[4], any_form, [&](int64_t id, int32_t lab) {
       if (nc < cap_cand) {
         cand_num[nc] = id;
         labels[nc] = lab;
@@ -222,6 +243,30 @@ int32_t nrms_behaviors_parse(const char* buf, int64_t len, const int64_t* capaci
   counts[2] = nh;
   counts[3] = (int64_t)users.size();
   return st;
+}
+
+}  // namespace
+
+int32_t nrms_behaviors_scan(const char* buf, int64_t len, int64_t* counts) {
+  return behaviors_scan(buf, len, counts, false);
+}
+
+int32_t nrms_behaviors_scan_any(const char* buf, int64_t len, int64_t* counts) {
+  return behaviors_scan(buf, len, counts, true);
+}
+
+int32_t nrms_behaviors_parse(const char* buf, int64_t len, const int64_t* capacity, int64_t* counts,
+                             int64_t* fields, int64_t* cand_num, int32_t* labels, int64_t* cand_count,
+                             int64_t* hist_num, int64_t* hist_count, int64_t* hist_user) {
+  return behaviors_parse(buf, len, capacity, counts, fields, cand_num, labels, cand_count, hist_num, hist_count,
+                         hist_user, false);
+}
+
+int32_t nrms_behaviors_parse_any(const char* buf, int64_t len, const int64_t* capacity, int64_t* counts,
+                                 int64_t* fields, int64_t* cand_num, int32_t* labels, int64_t* cand_count,
+                                 int64_t* hist_num, int64_t* hist_count, int64_t* hist_user) {
+  return behaviors_parse(buf, len, capacity, counts, fields, cand_num, labels, cand_count, hist_num, hist_count,
+                         hist_user, true);
 }
 
 // news_parsed.tsv: header with "id" and "title" columns; every row's title a

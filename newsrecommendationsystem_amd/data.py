@@ -231,17 +231,21 @@ def _ranges(starts, counts):
     return np.repeat(np.asarray(starts, np.int64) - off, counts) + np.arange(tot)
 
 
-def read_behaviors_native(path):
+def read_behaviors_native(path, any_form=False):
     """behaviors.tsv through the native reader (nrms_behaviors_scan /
     _parse: one C++ pass over the bytes) as a BehaviorsTable, or None when the
-    file is not in the plain MIND form (read_behaviors' general path)."""
+    file is not in the plain MIND form (read_behaviors' general path).
+    any_form: the nrms_behaviors_*_any pair, which also takes candidate tokens
+    without a label (MIND's test split); those get label -1."""
     import ctypes
     from . import _native as N
     lib = N.load()
+    scan = lib.nrms_behaviors_scan_any if any_form else lib.nrms_behaviors_scan
+    parse = lib.nrms_behaviors_parse_any if any_form else lib.nrms_behaviors_parse
     buf = _read_bytes(path)
     P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
     cap = np.zeros(3, np.int64)
-    st = lib.nrms_behaviors_scan(buf, len(buf), P(cap))
+    st = scan(buf, len(buf), P(cap))
     if st == N.NRMS_ERR_UNSUPPORTED:
         return None
     N.check(st, "nrms_behaviors_scan")
@@ -250,14 +254,23 @@ def read_behaviors_native(path):
     cand_num, labels, cand_count = np.empty(nc, np.int64), np.empty(nc, np.int32), np.empty(n, np.int64)
     hist_num, hist_count, hist_user = np.empty(nh, np.int64), np.empty(n, np.int64), np.empty(n, np.int64)
     counts = np.zeros(4, np.int64)
-    st = lib.nrms_behaviors_parse(buf, len(buf), P(cap), P(counts), P(fields), P(cand_num), P(labels),
-                                  P(cand_count), P(hist_num), P(hist_count), P(hist_user))
+    st = parse(buf, len(buf), P(cap), P(counts), P(fields), P(cand_num), P(labels),
+               P(cand_count), P(hist_num), P(hist_count), P(hist_user))
     if st == N.NRMS_ERR_UNSUPPORTED:
         return None
     N.check(st, "nrms_behaviors_parse")
     n, nc, nh = (int(x) for x in counts[:3])
     return BehaviorsTable(buf.decode("ascii"), fields[:n], cand_num[:nc], labels[:nc], cand_count[:n],
                           hist_num[:nh], hist_count[:n], hist_user[:n])
+
+
+def load_behaviors_any(path):
+    """behaviors.tsv of a split with or without labels (MIND's test split
+    lists bare ids): a BehaviorsTable from nrms_behaviors_*_any (label -1
+    where a token has none) for the plain MIND form, else read_behaviors'
+    list of Impression (whose raw cells parse_candidate_cells takes)."""
+    tab = read_behaviors_native(path, any_form=True)
+    return tab if tab is not None else read_behaviors(path)
 
 
 def load_behaviors(path):
@@ -412,6 +425,37 @@ def parse_impression_cells(impressions):
     labs = np.fromiter((y for im in impressions for y in im.labels), dtype=np.int64, count=len(names))
     counts = np.fromiter((len(im.candidates) for im in impressions), dtype=np.int64, count=n)
     return names, labs.astype(np.int32), counts
+
+
+def parse_candidate_cells(impressions):
+    """(candidate ids, per-impression counts) of a split, in order, labels
+    not needed: a token is `<id>-<label>` or a bare `<id>` (an unlabelled
+    split), and its id is the text before the first '-' (x.split('-')[0],
+    src/evaluate.py:154) or the whole token."""
+    n = len(impressions)
+    names = []
+    counts = np.empty(n, dtype=np.int64)
+    for k, im in enumerate(impressions):
+        toks = [t.split("-", 1)[0] for t in im.raw.split()] if im.raw is not None else list(im.candidates)
+        names += toks
+        counts[k] = len(toks)
+    return names, counts
+
+
+def news_numbers(names):
+    """int64 numbers of "N<digits>" ids (no leading zeros, at most 18 digits:
+    the form numeric_news_index indexes), or None if any id is of another form."""
+    n = len(names)
+    if not n:
+        return np.zeros(0, np.int64)
+    if max(map(len, names)) > 19:
+        return None
+    joined = " ".join(names)
+    if (joined.translate(_DIGITS) != " ".join(["N"] * n) or joined.count("N0") != joined.count("N0 ") + (
+            1 if joined.endswith("N0") else 0)):
+        return None
+    nums = np.array(joined.replace("N", "").split(), dtype=np.int64)
+    return nums if nums.size == n else None
 
 
 def history_ids(history_string, num_clicked=NUM_CLICKED):

@@ -53,21 +53,7 @@ class EvalPlan:
                 return
             impressions = list(tab)   # (ids not in the numeric form: the per-name path)
         self.impressions = impressions[:n]
-        # users keyed by history string, in first-seen order
-        hist_of = {}
-        hists = []
-        imp_user = np.empty(n, dtype=np.int64)
-        for k, im in enumerate(self.impressions):
-            u = hist_of.get(im.clicked_news)
-            if u is None:
-                u = hist_of[im.clicked_news] = len(hists)
-                hists.append(im.clicked_news)
-            imp_user[k] = u
-        rows_of = corpus.index   # news id -> first row (news2vector[...], evaluate.py:255)
-
-        def lookup(names):
-            return np.fromiter(map(rows_of.__getitem__, names), dtype=np.int64, count=len(names))
-
+        imp_user, hists = users_by_history(self.impressions)
         # MIND-form cells ("N<digits>-<label>"): one numeric parse and an array
         # index (data.candidate_rows_numeric); any other form: the per-name path
         nindex = numeric_news_index(corpus)
@@ -76,45 +62,78 @@ class EvalPlan:
             self.cand, self.labels, counts = fast
         else:
             cand_names, self.labels, counts = parse_impression_cells(self.impressions)
-            self.cand = lookup(cand_names).astype(np.int64) if cand_names else np.zeros(0, np.int64)
+            self.cand = lookup_rows(corpus, cand_names)
         self.pair_user = np.repeat(imp_user, counts)
         self.offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        hrows = history_rows_numeric(hists, nindex, num_clicked, pad)
-        if hrows is None:
-            hist_names = [x for h in hists for x in history_ids(h, num_clicked)]
-            real = np.array([x != PADDED_NEWS for x in hist_names], dtype=bool)
-            rows = np.full(len(hist_names), pad, dtype=np.int64)
-            if real.any():
-                rows[real] = lookup([x for x, r in zip(hist_names, real) if r])
-            hrows = rows.reshape(len(hists), num_clicked)
-        self.hist_rows = hrows
+        self.hist_rows = history_rows_of(corpus, hists, nindex, num_clicked)
 
     def _from_table(self, tab, nindex, num_clicked, pad):
         """The plan from a natively parsed split (data.BehaviorsTable): the
         same arrays as the Impression path's numeric fast path."""
         self.impressions = tab
-        n = len(tab)
         self.cand = _index_rows(nindex, tab.cand_num)
         self.labels = tab.labels
         counts = tab.cand_count
-        imp_user = tab.hist_user
-        self.pair_user = np.repeat(imp_user, counts)
+        self.pair_user = np.repeat(tab.hist_user, counts)
         self.offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        # each distinct history's first line: its first num_clicked ids, left-padded
-        _, first = np.unique(imp_user, return_index=True) if n else (None, np.zeros(0, np.int64))
-        U = first.size
-        hc, ho = tab.hist_count[first], tab.hist_off[first]
-        m = np.minimum(hc, num_clicked)
-        rows = np.full((U, num_clicked), pad, dtype=np.int64)
-        if int(m.sum()):
-            u = np.repeat(np.arange(U), m)
-            k = np.arange(int(m.sum())) - np.repeat(np.cumsum(m) - m, m)
-            rows[u, num_clicked - np.repeat(m, m) + k] = _index_rows(nindex, tab.hist_num[np.repeat(ho, m) + k])
-        self.hist_rows = rows
+        self.hist_rows = table_history_rows(tab, nindex, num_clicked, pad)
 
     @property
     def n_impressions(self):
         return len(self.offsets) - 1
+
+
+def users_by_history(impressions):
+    """(user index int64 per impression, the distinct history strings): users
+    are keyed by history string, numbered in first-seen order."""
+    hist_of = {}
+    hists = []
+    imp_user = np.empty(len(impressions), dtype=np.int64)
+    for k, im in enumerate(impressions):
+        u = hist_of.get(im.clicked_news)
+        if u is None:
+            u = hist_of[im.clicked_news] = len(hists)
+            hists.append(im.clicked_news)
+        imp_user[k] = u
+    return imp_user, hists
+
+
+def lookup_rows(corpus, names):
+    """corpus rows of news ids by name: id -> first row (news2vector[...],
+    evaluate.py:255); an unknown id raises KeyError."""
+    return np.fromiter(map(corpus.index.__getitem__, names), dtype=np.int64, count=len(names))
+
+
+def history_rows_of(corpus, hists, nindex, num_clicked):
+    """[len(hists), num_clicked] corpus rows of each history string's first
+    num_clicked ids, left-padded with len(corpus): the numeric pass when the
+    ids allow, the per-name lookup otherwise."""
+    pad = len(corpus)
+    hrows = history_rows_numeric(hists, nindex, num_clicked, pad)
+    if hrows is None:
+        hist_names = [x for h in hists for x in history_ids(h, num_clicked)]
+        real = np.array([x != PADDED_NEWS for x in hist_names], dtype=bool)
+        rows = np.full(len(hist_names), pad, dtype=np.int64)
+        if real.any():
+            rows[real] = lookup_rows(corpus, [x for x, r in zip(hist_names, real) if r])
+        hrows = rows.reshape(len(hists), num_clicked)
+    return hrows
+
+
+def table_history_rows(tab, nindex, num_clicked, pad):
+    """The same rows from a BehaviorsTable: each distinct history's first
+    line, its first num_clicked ids, left-padded."""
+    imp_user = tab.hist_user
+    _, first = np.unique(imp_user, return_index=True) if len(tab) else (None, np.zeros(0, np.int64))
+    U = first.size
+    hc, ho = tab.hist_count[first], tab.hist_off[first]
+    m = np.minimum(hc, num_clicked)
+    rows = np.full((U, num_clicked), pad, dtype=np.int64)
+    if int(m.sum()):
+        u = np.repeat(np.arange(U), m)
+        k = np.arange(int(m.sum())) - np.repeat(np.cumsum(m) - m, m)
+        rows[u, num_clicked - np.repeat(m, m) + k] = _index_rows(nindex, tab.hist_num[np.repeat(ho, m) + k])
+    return rows
 
 
 @torch.no_grad()
