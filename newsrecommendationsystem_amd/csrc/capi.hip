@@ -23,16 +23,6 @@ static int initial_gemm_arith() {
   return NRMS_GEMM_SPLIT_F16X3;
 }
 static std::atomic<int> g_gemm_arith{initial_gemm_arith()};
-// A/B switches of nrms_forward's launch folding (default on; "0" turns off):
-// NRMS_SPLIT_CLASSIFY -- the titles' classification in the pack launch and the
-// vocabulary projection's tail (titles.hpp) instead of a launch of its own
-// (the user dispatch order moves with it); NRMS_SCORE_FOLD -- the click scores
-// in the UserEncoder launch instead of the score kernel.
-static bool env_on(const char* name) {
-  const char* e = env_knob(name);
-  return !(e && e[0] == '0');
-}
-static const bool g_split_classify = env_on("NRMS_SPLIT_CLASSIFY");
 // test only (tests/test_gpu_parity.py): classification half A in the pack
 // launch but no tail jobs in the projection, so the news launch classifies
 // again itself -- the fallback nrms_forward takes when the projection leaves
@@ -41,7 +31,6 @@ static const bool g_skip_classify_tail = [] {
   const char* e = env_knob("NRMS_TEST_SKIP_CLASSIFY_TAIL");
   return e && e[0] == '1';
 }();
-static const bool g_score_fold = env_on("NRMS_SCORE_FOLD");
 static thread_local int32_t t_gemm_arith = -1;   // nrms_set_thread_gemm_arith (-1: none)
 int gemm_arith() {
   const int32_t t = t_gemm_arith;
@@ -65,19 +54,29 @@ constexpr int kQMax = 208;
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// Bump allocator over the caller's workspace.
+// Bump allocator over the caller's workspace. Every workspace and state
+// buffer has one layout routine, which takes a Carve and returns the named
+// pointers: run over() the caller's buffer it carves; run measuring (no base:
+// only off advances) it gives the size that buffer needs.
 struct Carve {
   char* base;
   size_t cap, off = 0;
   bool ok = true;
+  static Carve over(void* buf, size_t bytes) { return Carve{static_cast<char*>(buf), buf ? bytes : 0}; }
   float* floats(size_t n) {
     const size_t need = align_up(n * sizeof(float));
-    if (off + need > cap) { ok = false; return nullptr; }
-    float* p = reinterpret_cast<float*>(base + off);
+    if (need > cap - off) { ok = false; return nullptr; }
+    float* p = base ? reinterpret_cast<float*>(base + off) : nullptr;
     off += need;
     return p;
   }
 };
+template <class Layout>
+size_t measure(Layout&& layout) {
+  Carve cv{nullptr, SIZE_MAX};
+  layout(cv);
+  return cv.off;
+}
 
 bool weights_ok(const nrms_encoder_weights_t* w) {
   if (!w) return false;
@@ -104,14 +103,23 @@ WeightRows qkv_rows(const nrms_encoder_weights_t* w) {
   return r;
 }
 
+// one bias-free segment of `rows` rows (the backward GEMMs' transposed weights)
+WeightRows one_segment(const float* w, int rows, int accumulate) {
+  WeightRows r{};
+  r.w[0] = w;
+  r.seg_rows = rows;
+  r.nseg = 1;
+  r.accumulate = accumulate;
+  return r;
+}
+
 // q|k|v row stride of the hot path (nrms_qkv_row_stride; 3D since round 3)
+int64_t hot_ld(bool fused, int32_t D) { return fused ? qkv_row_stride(D) : 3 * (int64_t)D; }
 int64_t news_ld(const nrms_encoder_weights_t* w, int32_t L) {
-  return fused_news_supported(L, w->d_model, w->n_heads, w->query_dim) ? qkv_row_stride(w->d_model)
-                                                                         : 3 * (int64_t)w->d_model;
+  return hot_ld(fused_news_supported(L, w->d_model, w->n_heads, w->query_dim), w->d_model);
 }
 int64_t user_ld(const nrms_encoder_weights_t* w, int32_t N) {
-  return fused_user_supported(N, w->d_model, w->n_heads, w->query_dim) ? qkv_row_stride(w->d_model)
-                                                                        : 3 * (int64_t)w->d_model;
+  return hot_ld(fused_user_supported(N, w->d_model, w->n_heads, w->query_dim), w->d_model);
 }
 
 bool use_folded(int32_t mode, int64_t n_tok, int64_t V) {
@@ -120,73 +128,141 @@ bool use_folded(int32_t mode, int64_t n_tok, int64_t V) {
   return n_tok > V;
 }
 
-// Per-stage sizes (floats).
-struct NewsSizes {
-  size_t qkv, ctx, scores, wap, pack;
+// One encoder's workspace (nrms_news_encode[_folded], nrms_user_encode, and
+// both inside the forward's).
+struct EncodeWs {
+  float* qkv;      // projected rows, nrms_qkv_row_stride apart
+  float* ctx;      // stage kernels: attention context [rows][D]
+  float* scores;   // ... and additive scores [rows]
+  float* wap;      // the fused tail's workspace (packed W_add first)
+  float* pack;     // split Q|K|V weights (proj_x6_pack_floats)
 };
-NewsSizes news_sizes(int64_t n_titles, int32_t L, int64_t V, int32_t D, bool folded) {
-  const size_t ntok = (size_t)n_titles * (size_t)L;
-  return {(folded ? (size_t)V : ntok) * (size_t)qkv_row_stride(D), ntok * (size_t)D, ntok,
-          fused_news_workspace_floats(n_titles), proj_x6_pack_floats()};
+// rows: tokens (news) or clicked titles (user). qkv_rows: their own rows, V (the
+// folded table), or 0 with pack_floats 0 (the table is the caller's:
+// nrms_news_encode_folded; the state's: the prepared folded forward).
+EncodeWs encode_layout(Carve& cv, size_t qkv_rows, size_t rows, int32_t D, size_t wap_floats, size_t pack_floats) {
+  EncodeWs z{};
+  z.qkv = cv.floats(qkv_rows * (size_t)qkv_row_stride(D));
+  z.ctx = cv.floats(rows * (size_t)D);
+  z.scores = cv.floats(rows);
+  z.wap = cv.floats(wap_floats);
+  z.pack = cv.floats(pack_floats);
+  return z;
 }
-size_t news_bytes(const NewsSizes& z) {
-  return align_up(z.qkv * 4) + align_up(z.ctx * 4) + align_up(z.scores * 4) + align_up(z.wap * 4) +
-         align_up(z.pack * 4);
+EncodeWs news_encode_layout(Carve& cv, int64_t n_titles, int32_t L, int64_t qkv_rows, int32_t D) {
+  return encode_layout(cv, qkv_rows, (size_t)n_titles * (size_t)L, D, fused_news_workspace_floats(n_titles),
+                       proj_x6_pack_floats());
+}
+EncodeWs user_encode_layout(Carve& cv, int64_t B, int32_t N, int32_t D) {
+  return encode_layout(cv, (size_t)B * N, (size_t)B * N, D, fused_user_packed_b_floats(), proj_x6_pack_floats());
 }
 
+// nrms_forward[_prepared]'s workspace: both encoders', the news and user
+// vectors between them, and the UserEncoder's row list and dispatch order.
+// (A prepared step carves the buffers its state replaces all the same.)
+struct ForwardWs {
+  EncodeWs n;
+  float* news;   // [clicked B*N | candidates B*C] x D
+  float* user;   // [B][D]
+  EncodeWs u;
+  int64_t* ulist;    // [B*N] launch_user_row_list's rows
+  int32_t* uorder;   // [B] user dispatch order
+};
+ForwardWs forward_layout(Carve& cv, int64_t B, int32_t C, int32_t N, int32_t L, int64_t qkv_rows, int32_t D) {
+  const int64_t n_all = B * (C + N);
+  ForwardWs z{};
+  z.n = news_encode_layout(cv, n_all, L, qkv_rows, D);
+  z.news = cv.floats((size_t)n_all * D);
+  z.user = cv.floats((size_t)B * D);
+  z.u = user_encode_layout(cv, B, N, D);
+  z.ulist = reinterpret_cast<int64_t*>(cv.floats((size_t)B * N * 2));
+  z.uorder = reinterpret_cast<int32_t*>(cv.floats((size_t)B));
+  return z;
+}
+size_t forward_bytes(int64_t B, int32_t C, int32_t N, int32_t L, int64_t qkv_rows, int32_t D) {
+  if (B < 0 || C < 0 || N <= 0 || L <= 0 || qkv_rows < 0 || D <= 0) return 0;
+  return measure([&](Carve& cv) { forward_layout(cv, B, C, N, L, qkv_rows, D); });
+}
+
+// The weight-derived buffers of a forward: the folded table, both encoders'
+// split Q|K|V weights and both packed W_add -- carved from a caller's state
+// buffer (nrms_forward_prepare / nrms_forward_prepared) or part of
+// nrms_forward's own workspace.
+struct WeightState {
+  float* table;   // [V][ld] (null: none)
+  float* pack;    // news Q|K|V (proj_x6_pack_floats)
+  float* upack;   // user Q|K|V
+  float* nwap;    // news W_add planes + the zero / NaN rows (fused_news_packed_floats)
+  float* uwap;    // user W_add (fused_user_packed_b_floats)
+};
+WeightState state_layout(Carve& cv, int64_t V, int32_t D, bool with_table) {
+  WeightState ws{};
+  if (with_table) ws.table = cv.floats((size_t)V * (size_t)qkv_row_stride(D));
+  ws.pack = cv.floats(proj_x6_pack_floats());
+  ws.upack = cv.floats(proj_x6_pack_floats());
+  ws.nwap = cv.floats(fused_news_packed_floats());
+  ws.uwap = cv.floats(fused_user_packed_b_floats());
+  return ws;
+}
+
+// The training calls' workspaces.
+struct AdditiveBackwardWs {
+  float *dz, *waT, *part_rows, *part_tn;
+};
+AdditiveBackwardWs additive_backward_layout(Carve& cv, int64_t n_seq, int32_t L, int32_t D, int32_t Q) {
+  return {cv.floats((size_t)n_seq * L * Q), cv.floats((size_t)D * Q),   // (braces: in this order)
+          cv.floats(additive_backward_part_floats(n_seq, Q)), cv.floats(gemm_tn_part_floats(Q, D))};
+}
+struct ProjectBackwardWs {
+  float *wT, *part_tn;
+};
+ProjectBackwardWs project_backward_layout(Carve& cv, int32_t D) {
+  return {cv.floats((size_t)3 * D * D), cv.floats(gemm_tn_part_floats(3 * D, D))};
+}
+
+AdditiveWeights additive(const nrms_encoder_weights_t* w) { return AdditiveWeights{w->w_add, w->b_add, w->q_add}; }
+
 // Q|K|V projection of the encoders: the pre-split-W kernel (proj_x6.hip) when
-// the shape and arithmetic allow, packing w into `pack` first unless the
-// caller already did (packed = true, with the same arith); the staged GEMM
+// the shape and arithmetic allow, packing w into o.pack first unless the
+// caller already did (o.packed, with the same arith); the staged GEMM
 // otherwise (x6: bitwise the same rows; f16x3: the kernel's scaled split-f16
-// arithmetic, the staged GEMM's x6 rows only within rounding). list_count
-// non-null: row-list mode (launch_gemm_store_list). arith < 0: the current mode.
-int32_t project_qkv(const float* X, int64_t n_rows_x, ARows ar, const int64_t* row_ids, int64_t M,
-                    const nrms_encoder_weights_t* w, float* pack, bool packed, float* Y, int64_t ld,
-                    hipStream_t s, const int32_t* list_count = nullptr, int arith = -1,
-                    const tl::TailJobs* tail = nullptr, bool* tail_done = nullptr) {
+// arithmetic, the staged GEMM's x6 rows only within rounding).
+Launched project_qkv(const ProjRows& in, const nrms_encoder_weights_t* w, float* Y, int64_t ld, hipStream_t s,
+                     const ProjOpts& o) {
   const int D = w->d_model;
   const WeightRows wr = qkv_rows(w);
-  if (arith < 0) arith = gemm_arith();
+  const int arith = o.arith < 0 ? gemm_arith() : o.arith;
   const bool h3 = arith == NRMS_GEMM_SPLIT_F16X3;
-  if (tail_done) *tail_done = false;
-  if (pack && arith != NRMS_GEMM_F32 && proj_x6_supported(D, 3 * D, wr) && ((uintptr_t)Y % 16) == 0 &&
+  if (o.pack && arith != NRMS_GEMM_F32 && proj_x6_supported(D, 3 * D, wr) && ((uintptr_t)Y % 16) == 0 &&
       ld % 4 == 0) {
-    if (!packed)
-      if (int32_t st = launch_proj_x6_pack(wr, pack, nullptr, nullptr, h3, s)) return st;
-    const int32_t st = launch_proj_x6(X, n_rows_x, ar, row_ids, M, pack, Y, ld, list_count, h3, s, tail);
-    if (tail_done) *tail_done = st == NRMS_OK && tail != nullptr;
-    return st;
+    if (!o.packed)
+      if (int32_t st = launch_proj_x6_pack(wr, o.pack, nullptr, nullptr, h3, s)) return st;
+    Launched did = launch_proj_x6(in.X, in.n_rows_x, in.ar, in.row_ids, in.M, o.pack, Y, ld, o.list_count, h3, s,
+                                  o.tail);
+    did.tail_done = did.st == NRMS_OK && o.tail != nullptr;
+    return did;
   }
-  if (list_count) return launch_gemm_store_list(X, n_rows_x, row_ids, list_count, M, D, wr, 3 * D, Y, ld, s);
-  return launch_gemm_store_rows(X, n_rows_x, ar, row_ids, M, D, wr, 3 * D, Y, ld, s);
+  if (o.list_count)
+    return launch_gemm_store_list(in.X, in.n_rows_x, in.row_ids, o.list_count, in.M, D, wr, 3 * D, Y, ld, s);
+  return launch_gemm_store_rows(in.X, in.n_rows_x, in.ar, in.row_ids, in.M, D, wr, 3 * D, Y, ld, s);
 }
 
 // attention + additive pooling from projected rows (shared by news and user
-// paths). `wap` non-null: use the fused news kernel when the geometry allows.
-int32_t encode_from_qkv(const float* qkv, int64_t ldq, int64_t n_rows, const int64_t* ids_a,
-                        int64_t n_seq_a, const int64_t* ids_b, int64_t n_seq, int32_t L,
-                        const nrms_encoder_weights_t* w, float* ctx, float* scores, float* out,
-                        hipStream_t s, float* wap = nullptr, bool* deduped = nullptr,
-                        int64_t broadcast_from = 0, int64_t* user_list = nullptr, int64_t user_rows = 0,
-                        bool prepacked = false, bool direct_rows = false, bool* classified = nullptr,
-                        bool preclassified = false, float* step_ws = nullptr) {
+// paths). o.wap non-null: use the fused news kernel when the geometry allows.
+Launched encode_from_qkv(const QkvRows& qkv, TitleIds ids, int32_t L, const nrms_encoder_weights_t* w, float* out,
+                         hipStream_t s, const EncodeOpts& o) {
   const int D = w->d_model;
-  if (deduped) *deduped = false;
-  if (classified) *classified = false;
-  if (wap && fused_news_supported(L, D, w->n_heads, w->query_dim))
-    return launch_fused_news(qkv, ldq, n_rows, ids_a, n_seq_a, ids_b, n_seq, w->w_add, w->b_add,
-                             w->q_add, wap, out, s, -1, deduped, broadcast_from, user_list, user_rows,
-                             prepacked, direct_rows, -1, classified, preclassified, step_ws);
-  if (preclassified) return NRMS_ERR_INVALID_ARG;
-  if (direct_rows) ids_a = ids_b = nullptr;   // per-token rows: the ids only classify (fused kernel)
+  if (o.wap && fused_news_supported(L, D, w->n_heads, w->query_dim))
+    return launch_fused_news(qkv, ids, additive(w), o.wap, out, s, o.news);
+  if (o.news.preclassified) return NRMS_ERR_INVALID_ARG;
+  if (o.news.direct_rows) ids.a = ids.b = nullptr;   // per-token rows: the ids only classify (fused kernel)
   // stage kernels: any row stride >= 3D (packed rows, or the folded table's
   // rows of nrms_qkv_row_stride)
-  int32_t st = launch_mhsa(qkv, ldq, n_rows, ids_a, n_seq_a, ids_b, n_seq, L, w->n_heads, kDK, ctx, s);
+  int32_t st = launch_mhsa(qkv.p, qkv.ld, qkv.n_rows, ids.a, ids.n_a, ids.b, ids.n, L, w->n_heads, kDK, o.ctx, s);
   if (st) return st;
-  st = launch_gemm_additive_score(ctx, n_seq * L, D, w->w_add, w->b_add, w->q_add, w->query_dim,
-                                  scores, s);
+  st = launch_gemm_additive_score(o.ctx, ids.n * L, D, w->w_add, w->b_add, w->q_add, w->query_dim, o.scores, s);
   if (st) return st;
-  return launch_additive_pool(ctx, scores, n_seq, L, D, out, s);
+  return launch_additive_pool(o.ctx, o.scores, ids.n, L, D, out, s);
 }
 
 }  // namespace
@@ -263,7 +339,7 @@ int32_t nrms_qkv_project(const float* x, int64_t n_rows_x, const int64_t* row_id
 }
 
 size_t nrms_qkv_project_workspace_size(int32_t D) {
-  return D > 0 ? align_up(proj_x6_pack_floats() * 4) : 0;
+  return D > 0 ? measure([](Carve& cv) { cv.floats(proj_x6_pack_floats()); }) : 0;
 }
 
 int32_t nrms_qkv_project_ws(const float* x, int64_t n_rows_x, const int64_t* row_ids, int64_t M,
@@ -276,10 +352,10 @@ int32_t nrms_qkv_project_ws(const float* x, int64_t n_rows_x, const int64_t* row
   if (ld_qkv == 0) ld_qkv = 3 * D;
   if (ld_qkv < 3 * D) return NRMS_ERR_INVALID_ARG;
   if (M == 0) return NRMS_OK;
-  Carve cv{static_cast<char*>(workspace), workspace ? workspace_bytes : 0};
+  Carve cv = Carve::over(workspace, workspace_bytes);
   float* pack = cv.floats(proj_x6_pack_floats());
   if (!cv.ok) return NRMS_ERR_WORKSPACE;
-  return project_qkv(x, n_rows_x, contiguous_rows(D), row_ids, M, w, pack, false, qkv, ld_qkv, stream);
+  return project_qkv({x, n_rows_x, contiguous_rows(D), row_ids, M}, w, qkv, ld_qkv, stream, {.pack = pack}).st;
 }
 
 int32_t nrms_self_attention(const float* qkv, int64_t n_rows_qkv, const int64_t* tok_ids,
@@ -323,7 +399,8 @@ int32_t nrms_additive_pool(const float* x, const float* scores, int64_t n_seq, i
 
 size_t nrms_news_attention_pool_workspace_size(int64_t n_titles, int32_t L, int32_t D) {
   if (n_titles < 0 || L <= 0 || D <= 0) return 0;
-  return align_up(fused_news_workspace_floats(n_titles) * 4);   // the context stays on chip
+  // (the context stays on chip)
+  return measure([&](Carve& cv) { cv.floats(fused_news_workspace_floats(n_titles)); });
 }
 
 int32_t nrms_news_attention_pool(const float* qkv, int64_t ld_qkv, int64_t n_rows_qkv,
@@ -336,19 +413,19 @@ int32_t nrms_news_attention_pool(const float* qkv, int64_t ld_qkv, int64_t n_row
   if (!fused_news_supported(L, w->d_model, w->n_heads, w->query_dim)) return NRMS_ERR_UNSUPPORTED;
   if (n_titles == 0) return NRMS_OK;
   if (!qkv || !out) return NRMS_ERR_INVALID_ARG;
-  Carve cv{static_cast<char*>(workspace), workspace ? workspace_bytes : 0};
+  Carve cv = Carve::over(workspace, workspace_bytes);
   float* wap = cv.floats(fused_news_workspace_floats(n_titles));
   if (!cv.ok) return NRMS_ERR_WORKSPACE;
   if (ld_qkv == 0) ld_qkv = 3 * (int64_t)w->d_model;
-  return launch_fused_news(qkv, ld_qkv, n_rows_qkv, tok_ids, n_seq_a, tok_ids_b, n_titles, w->w_add,
-                           w->b_add, w->q_add, wap, out, stream);
+  return launch_fused_news({qkv, ld_qkv, n_rows_qkv}, {tok_ids, n_seq_a, tok_ids_b, n_titles}, additive(w), wap, out,
+                           stream).st;
 }
 
 size_t nrms_news_encode_workspace_size(int64_t n_titles, int32_t L, int64_t V, int32_t D,
                                        int32_t proj_mode) {
   if (n_titles < 0 || L <= 0 || V < 0 || D <= 0) return 0;
-  const bool folded = use_folded(proj_mode, n_titles * L, V);
-  return news_bytes(news_sizes(n_titles, L, V, D, folded));
+  const int64_t qkv_rows = use_folded(proj_mode, n_titles * L, V) ? V : n_titles * L;
+  return measure([&](Carve& cv) { news_encode_layout(cv, n_titles, L, qkv_rows, D); });
 }
 
 int32_t nrms_news_encode(const int64_t* ids, int64_t n_titles, int32_t L, const float* table,
@@ -359,36 +436,24 @@ int32_t nrms_news_encode(const int64_t* ids, int64_t n_titles, int32_t L, const 
   if (n_titles == 0) return NRMS_OK;
   if (!ids || !table || !out) return NRMS_ERR_INVALID_ARG;
   const int D = w->d_model;
+  // Vocabulary-level projection: one GEMM over the table, then rows gathered by
+  // id; or per-token projection with the embedding gather fused into the
+  // A-operand load.
   const bool folded = use_folded(proj_mode, n_titles * L, V);
-  const NewsSizes z = news_sizes(n_titles, L, V, D, folded);
-  const int64_t ld = news_ld(w, L);
-  Carve cv{static_cast<char*>(workspace), workspace ? workspace_bytes : 0};
-  float* qkv = cv.floats(z.qkv);
-  float* ctx = cv.floats(z.ctx);
-  float* scores = cv.floats(z.scores);
-  float* wap = cv.floats(z.wap);
-  float* pack = cv.floats(z.pack);
+  const int64_t ld = news_ld(w, L), rows = folded ? V : n_titles * L;
+  Carve cv = Carve::over(workspace, workspace_bytes);
+  const EncodeWs z = news_encode_layout(cv, n_titles, L, rows, D);
   if (!cv.ok) return NRMS_ERR_WORKSPACE;
-  int32_t st;
-  if (folded) {
-    // Vocabulary-level projection: one GEMM over the table, then rows gathered by id.
-    st = project_qkv(table, V, contiguous_rows(D), nullptr, V, w, pack, false, qkv, ld, stream);
-    if (st) return st;
-    return encode_from_qkv(qkv, ld, V, ids, n_titles, nullptr, n_titles, L, w, ctx, scores, out,
-                           stream, wap);
-  }
-  // Per-token projection with the embedding gather fused into the A-operand load.
-  st = project_qkv(table, V, contiguous_rows(D), ids, n_titles * L, w, pack, false, qkv, ld, stream);
-  if (st) return st;
-  return encode_from_qkv(qkv, ld, n_titles * L, ids, n_titles, nullptr, n_titles, L, w, ctx,
-                         scores, out, stream, wap, nullptr, 0, nullptr, 0, false, /*direct_rows=*/true);
+  const ProjRows in{table, V, contiguous_rows(D), folded ? nullptr : ids, rows};
+  if (int32_t st = project_qkv(in, w, z.qkv, ld, stream, {.pack = z.pack}).st) return st;
+  EncodeOpts eo{z.ctx, z.scores, z.wap};
+  eo.news.direct_rows = !folded;
+  return encode_from_qkv({z.qkv, ld, rows}, {ids, n_titles, nullptr, n_titles}, L, w, out, stream, eo).st;
 }
 
 size_t nrms_news_encode_folded_workspace_size(int64_t n_titles, int32_t L, int32_t D) {
   if (n_titles < 0 || L <= 0 || D <= 0) return 0;
-  const size_t ntok = (size_t)n_titles * L;
-  return align_up(ntok * D * 4) + align_up(ntok * 4) +
-         align_up(fused_news_workspace_floats(n_titles) * 4);
+  return measure([&](Carve& cv) { encode_layout(cv, 0, (size_t)n_titles * L, D, fused_news_workspace_floats(n_titles), 0); });
 }
 
 int32_t nrms_news_encode_folded(const int64_t* ids, int64_t n_titles, int32_t L,
@@ -399,27 +464,23 @@ int32_t nrms_news_encode_folded(const int64_t* ids, int64_t n_titles, int32_t L,
   if (int32_t st = shape_ok(w)) return st;
   if (n_titles == 0) return NRMS_OK;
   if (!ids || !qkv_table || !out) return NRMS_ERR_INVALID_ARG;
-  const size_t ntok = (size_t)n_titles * L;
-  Carve cv{static_cast<char*>(workspace), workspace ? workspace_bytes : 0};
-  float* ctx = cv.floats(ntok * w->d_model);
-  float* scores = cv.floats(ntok);
-  float* wap = cv.floats(fused_news_workspace_floats(n_titles));
+  Carve cv = Carve::over(workspace, workspace_bytes);
+  const EncodeWs z = encode_layout(cv, 0, (size_t)n_titles * L, w->d_model, fused_news_workspace_floats(n_titles), 0);
   if (!cv.ok) return NRMS_ERR_WORKSPACE;
   if (ld_qkv == 0) ld_qkv = 3 * (int64_t)w->d_model;
-  return encode_from_qkv(qkv_table, ld_qkv, V, ids, n_titles, nullptr, n_titles, L, w, ctx, scores,
-                         out, stream, wap);
+  return encode_from_qkv({qkv_table, ld_qkv, V}, {ids, n_titles, nullptr, n_titles}, L, w, out, stream,
+                         {z.ctx, z.scores, z.wap})
+      .st;
 }
 
 size_t nrms_user_encode_workspace_size(int64_t B, int32_t N, int32_t D) {
   if (B < 0 || N <= 0 || D <= 0) return 0;
-  const size_t rows = (size_t)B * N;
-  return align_up(rows * (size_t)qkv_row_stride(D) * 4) + align_up(rows * D * 4) + align_up(rows * 4) +
-         align_up(fused_user_packed_b_floats() * 4) + align_up(proj_x6_pack_floats() * 4);
+  return measure([&](Carve& cv) { user_encode_layout(cv, B, N, D); });
 }
 
 size_t nrms_user_attention_pool_workspace_size(int64_t B, int32_t N, int32_t D) {
   if (B < 0 || N <= 0 || D <= 0) return 0;
-  return align_up(fused_user_packed_b_floats() * 4);
+  return measure([](Carve& cv) { cv.floats(fused_user_packed_b_floats()); });
 }
 
 int32_t nrms_user_attention_pool(const float* qkv, int64_t ld_qkv, int64_t B, int32_t N,
@@ -430,11 +491,11 @@ int32_t nrms_user_attention_pool(const float* qkv, int64_t ld_qkv, int64_t B, in
   if (!fused_user_supported(N, w->d_model, w->n_heads, w->query_dim)) return NRMS_ERR_UNSUPPORTED;
   if (B == 0) return NRMS_OK;
   if (!qkv || !out) return NRMS_ERR_INVALID_ARG;
-  Carve cv{static_cast<char*>(workspace), workspace ? workspace_bytes : 0};
+  Carve cv = Carve::over(workspace, workspace_bytes);
   float* wap = cv.floats(fused_user_packed_b_floats());
   if (!cv.ok) return NRMS_ERR_WORKSPACE;
   if (ld_qkv == 0) ld_qkv = 3 * (int64_t)w->d_model;
-  return launch_fused_user(qkv, ld_qkv, B, N, w->w_add, w->b_add, w->q_add, wap, out, stream);
+  return launch_fused_user({qkv, ld_qkv}, B, N, additive(w), wap, out, stream);
 }
 
 int32_t nrms_user_attention_pool_padded(const float* qkv, int64_t ld_qkv, int64_t B, int32_t N,
@@ -445,14 +506,14 @@ int32_t nrms_user_attention_pool_padded(const float* qkv, int64_t ld_qkv, int64_
   if (!fused_user_supported(N, w->d_model, w->n_heads, w->query_dim)) return NRMS_ERR_UNSUPPORTED;
   if (B == 0) return NRMS_OK;
   if (!qkv || !out || !pad_flags) return NRMS_ERR_INVALID_ARG;
-  Carve cv{static_cast<char*>(workspace), workspace ? workspace_bytes : 0};
+  Carve cv = Carve::over(workspace, workspace_bytes);
   float* wap = cv.floats(fused_user_packed_b_floats());
   if (!cv.ok) return NRMS_ERR_WORKSPACE;
   if (ld_qkv == 0) ld_qkv = 3 * (int64_t)w->d_model;
   const bool compact = token_compaction() && N <= 64;
   const PaddingGroups pg{pad_flags, nullptr, nullptr};   // (no rep: every flagged row was projected)
-  return launch_fused_user(qkv, ld_qkv, B, N, w->w_add, w->b_add, w->q_add, wap, out, stream,
-                           compact ? &pg : nullptr, false, false, compact);
+  return launch_fused_user({qkv, ld_qkv}, B, N, additive(w), wap, out, stream,
+                           {.pg = compact ? &pg : nullptr, .compact = compact});
 }
 
 int32_t nrms_user_encode(const float* clicked, int64_t B, int32_t N, int64_t stride_b,
@@ -464,23 +525,18 @@ int32_t nrms_user_encode(const float* clicked, int64_t B, int32_t N, int64_t str
   if (!clicked || !out) return NRMS_ERR_INVALID_ARG;
   const int D = w->d_model;
   const int64_t rows = B * N;
-  Carve cv{static_cast<char*>(workspace), workspace ? workspace_bytes : 0};
+  Carve cv = Carve::over(workspace, workspace_bytes);
   const int64_t ld = user_ld(w, N);
-  float* qkv = cv.floats((size_t)rows * (size_t)ld);
-  float* ctx = cv.floats((size_t)rows * D);
-  float* scores = cv.floats((size_t)rows);
-  float* wap = cv.floats(fused_user_packed_b_floats());
-  float* pack = cv.floats(proj_x6_pack_floats());
+  const EncodeWs z = user_encode_layout(cv, B, N, D);
   if (!cv.ok) return NRMS_ERR_WORKSPACE;
   // the [B, N, D] view is read in place (e.g. the transpose(0, 1) of
   // src/evaluate.py:220-224: stride_b = D, stride_n = B * D)
   const ARows ar = (stride_b == (int64_t)N * D && stride_n == D) ? contiguous_rows(D)
                                                                  : ARows{N, stride_b, stride_n};
-  int32_t st = project_qkv(clicked, rows, ar, nullptr, rows, w, pack, false, qkv, ld, stream);
-  if (st) return st;
+  if (int32_t st = project_qkv({clicked, rows, ar, nullptr, rows}, w, z.qkv, ld, stream, {.pack = z.pack}).st) return st;
   if (fused_user_supported(N, D, w->n_heads, w->query_dim) && ((uintptr_t)out % 16) == 0)
-    return launch_fused_user(qkv, ld, B, N, w->w_add, w->b_add, w->q_add, wap, out, stream);
-  return encode_from_qkv(qkv, ld, rows, nullptr, B, nullptr, B, N, w, ctx, scores, out, stream);
+    return launch_fused_user({z.qkv, ld}, B, N, additive(w), z.wap, out, stream);
+  return encode_from_qkv({z.qkv, ld, rows}, {nullptr, B, nullptr, B}, N, w, out, stream, {z.ctx, z.scores}).st;
 }
 
 int32_t nrms_score(const float* news, int64_t B, int32_t C, int64_t stride_b, int64_t stride_c,
@@ -544,269 +600,306 @@ int32_t nrms_impression_metrics(const float* scores, const int32_t* labels,
 
 size_t nrms_forward_workspace_size(int64_t B, int32_t C, int32_t N, int32_t L, int64_t V,
                                    int32_t D, int32_t proj_mode) {
-  if (B < 0 || C < 0 || N <= 0 || L <= 0 || V < 0 || D <= 0) return 0;
-  const int64_t n_all = B * (C + N);
-  return nrms_news_encode_workspace_size(n_all, L, V, D, proj_mode) +
-         align_up((size_t)n_all * D * 4) + align_up((size_t)B * D * 4) +
-         nrms_user_encode_workspace_size(B, N, D) + align_up((size_t)B * N * 8) + align_up((size_t)B * 4);
+  if (V < 0) return 0;
+  const int64_t n_tok = B * (C + N) * L;
+  return forward_bytes(B, C, N, L, use_folded(proj_mode, n_tok, V) ? V : n_tok, D);
 }
 
 size_t nrms_forward_state_size(int64_t V, int32_t D, int32_t with_folded_table) {
   if (V < 0 || D <= 0) return 0;
-  return (with_folded_table ? align_up((size_t)V * (size_t)qkv_row_stride(D) * 4) : 0) +
-         2 * align_up(proj_x6_pack_floats() * 4) + align_up(fused_news_packed_floats() * 4) +
-         align_up(fused_user_packed_b_floats() * 4);
+  return measure([&](Carve& cv) { state_layout(cv, V, D, with_folded_table != 0); });
 }
+
+}  // extern "C"
 
 namespace {
 
-// The weight-derived buffers of a forward: the folded table, both encoders'
-// split Q|K|V weights and both packed W_add -- carved from a caller's state
-// buffer (nrms_forward_prepare / nrms_forward_prepared) or from nrms_forward's
-// own workspace.
-struct WeightState {
-  float* table;   // [V][ld] (null: none)
-  float* pack;    // news Q|K|V (proj_x6_pack_floats)
-  float* upack;   // user Q|K|V
-  float* nwap;    // news W_add planes + the zero / NaN rows (fused_news_packed_floats)
-  float* uwap;    // user W_add (fused_user_packed_b_floats)
-};
-
-bool carve_state(void* buf, size_t bytes, int64_t V, int32_t D, bool with_table, WeightState* ws) {
-  Carve cv{static_cast<char*>(buf), buf ? bytes : 0};
-  ws->table = with_table ? cv.floats((size_t)V * (size_t)qkv_row_stride(D)) : nullptr;
-  ws->pack = cv.floats(proj_x6_pack_floats());
-  ws->upack = cv.floats(proj_x6_pack_floats());
-  ws->nwap = cv.floats(fused_news_packed_floats());
-  ws->uwap = cv.floats(fused_user_packed_b_floats());
-  return cv.ok;
-}
-
-// Everything of a forward that reads weights only, enqueued on the stream:
-// add_packs: all four packings in one launch; else, packed: the two Q|K|V
-// packs; want_table: the vocabulary projection into ws.table. nrms_forward
-// passes the launch folding of its own step along (cjob + counters: the
-// counter reset and classification half A in the pack launch; tail: half B in
-// the projection's tail); nrms_forward_prepare passes none, so nothing here
-// depends on an id.
-int32_t prepare_weights(const float* table, int64_t V, const nrms_encoder_weights_t* news_w,
-                        const nrms_encoder_weights_t* user_w, int arith, bool packed, bool add_packs,
-                        bool want_table, const WeightState& ws, int64_t ld, hipStream_t stream,
-                        const tl::ClassifyJob* cjob = nullptr, int32_t* counters = nullptr,
-                        const tl::TailJobs* tail = nullptr, bool* tail_done = nullptr) {
-  const int D = news_w->d_model;
-  const WeightRows nwr = qkv_rows(news_w), uwr = qkv_rows(user_w);
-  const bool h3 = arith == NRMS_GEMM_SPLIT_F16X3;
-  if (tail_done) *tail_done = false;
-  if (add_packs) {
-    if (int32_t st = launch_forward_pack(nwr, ws.pack, uwr, ws.upack, news_w->w_add, ws.nwap, h3, user_w->w_add,
-                                         ws.uwap, stream, cjob, counters))
-      return st;
-  } else if (packed) {
-    if (int32_t st = launch_proj_x6_pack(nwr, ws.pack, &uwr, ws.upack, h3, stream)) return st;
-  }
-  if (!want_table) return NRMS_OK;
-  return project_qkv(table, V, contiguous_rows(D), nullptr, V, news_w, ws.pack, packed, ws.table, ld, stream,
-                     nullptr, arith, tail, tail_done);
-}
-
-// nrms_forward[_timed] (state null: the weight-derived buffers are carved from
-// the workspace and prepared first, with the step's classification folded into
-// those launches) and nrms_forward_prepared[_timed] (state: they are read from
-// it, and the step starts with the classification's own two launches). ev
-// (optional, NRMS_FORWARD_STAGES + 1 events): recorded on the stream before
-// each stage and after the last.
-int32_t forward_impl(const int64_t* cand_ids, const int64_t* clicked_ids, int64_t B, int32_t C,
-                     int32_t N, int32_t L, const float* table, int64_t V,
-                     const nrms_encoder_weights_t* news_w, const nrms_encoder_weights_t* user_w,
-                     int32_t proj_mode, float* logits, void* workspace, size_t workspace_bytes,
-                     hipStream_t stream, hipEvent_t* ev, const nrms_forward_state_t* state, bool prepared) {
-  if (B < 0 || C < 0 || N <= 0 || L <= 0 || V <= 0) return NRMS_ERR_INVALID_ARG;
+// The checks nrms_forward_prepare and every forward share.
+int32_t encoders_ok(int64_t V, const nrms_encoder_weights_t* news_w, const nrms_encoder_weights_t* user_w) {
+  if (V <= 0) return NRMS_ERR_INVALID_ARG;
   if (int32_t st = shape_ok(news_w)) return st;
   if (int32_t st = shape_ok(user_w)) return st;
-  if (news_w->d_model != user_w->d_model) return NRMS_ERR_INVALID_ARG;
-  const int D = news_w->d_model;
-  const int64_t n_clk = B * N, n_all = B * (C + N);
-  const bool folded = use_folded(proj_mode, n_all * L, V);
-  const int arith = gemm_arith();
-  WeightState sw{};
-  if (prepared) {
-    if (!state || !state->buffer || state->V != V || state->D != D || state->gemm_arith != arith)
-      return NRMS_ERR_INVALID_ARG;
-    const bool has_table = (state->flags & NRMS_STATE_FOLDED_TABLE) != 0;
-    if (folded && !has_table) return NRMS_ERR_INVALID_ARG;
-    if (state->ld_qkv != qkv_row_stride(D)) return NRMS_ERR_INVALID_ARG;
-    if (state->bytes < nrms_forward_state_size(V, D, has_table) ||
-        !carve_state(state->buffer, state->bytes, V, D, has_table, &sw))
-      return NRMS_ERR_WORKSPACE;
+  return news_w->d_model == user_w->d_model ? NRMS_OK : NRMS_ERR_INVALID_ARG;
+}
+// both encoders' Q|K|V are split once into packs (proj_x6.hip) under this arithmetic
+bool qkv_packs(int arith, const nrms_encoder_weights_t* news_w) {
+  return arith != NRMS_GEMM_F32 && proj_x6_supported(news_w->d_model, 3 * news_w->d_model, qkv_rows(news_w));
+}
+
+// A forward call's arguments (prepared: nrms_forward_prepared[_timed], which
+// read the weight-derived buffers from `state`).
+struct ForwardArgs {
+  const int64_t *cand_ids, *clicked_ids;
+  int64_t B;
+  int32_t C, N, L;
+  const float* table;
+  int64_t V;
+  const nrms_encoder_weights_t *news_w, *user_w;
+  int32_t proj_mode;
+  float* logits;
+  void* workspace;
+  size_t workspace_bytes;
+  const nrms_forward_state_t* state;
+  bool prepared;
+};
+
+// Everything a forward step decides before its first launch (pipeline.py's
+// ForwardPlan picks the shapes; this, the launches). What the launches
+// themselves report (Launched) stays with the run.
+struct StepLaunchPlan {
+  bool empty;   // B == 0: nothing to launch
+  int D, arith;
+  int64_t n_clk, n_all;
+  bool folded;
+  ForwardWs ws;
+  // The weight-derived buffers: the step's own workspace, which its first
+  // launches fill with the step's classification folded into them
+  // (fill_weights: nrms_forward); or the caller's state wherever it has them,
+  // the step then starting with the classification's own two launches.
+  WeightState wt;
+  bool fill_weights;
+  float* qkv;        // the news rows: wt.table (folded) or per-token rows
+  int64_t ld, uld;   // news / user q|k|v row strides
+  float* step_ws;    // the news launch's own part of ws.n.wap
+  bool packed;       // both encoders' Q|K|V come from packs
+  bool prepacked;    // ... and both W_add are packed before the news launch
+  bool user_fused;
+  // with the UserEncoder's row-list projection the clicked padding titles'
+  // vectors are never read, and the scorer reads a copied candidate from the
+  // rep group: no copies are written, and the news kernel lists the
+  // UserEncoder's rows in its prologue
+  bool user_rows_here;
+  // the titles' classification without the atomics (titles.hpp): the first
+  // half with the counter reset and the second (classify_tail) in the
+  // vocabulary projection's tail or a launch of its own; without the second
+  // half the news launch classifies the titles itself
+  bool split_cls, classify_tail;
+  tl::ClassifyJob cjob;
+  tl::TailJobs ntail;
+  // if the news launch classifies: UserEncoder token compaction
+  // (user_fused.hip: a user's padding positions, one news vector, collapse into
+  // one row carrying their count), and the users' longest-first dispatch order
+  // in the UserEncoder projection's tail (titles.hpp)
+  bool user_compact, order_tail;
+  // the click scores in the fused UserEncoder launch (bitwise the score
+  // kernel's; its stage is then empty)
+  bool score_fold;
+};
+
+// Everything of a forward that reads weights only, enqueued on the stream into
+// p.wt: prepacked: all four packings in one launch; else, packed: the two
+// Q|K|V packs; folded: the vocabulary projection into wt.table. nrms_forward's
+// plan folds its step's classification into these launches (split_cls: the
+// counter reset and half A in the pack launch; classify_tail: half B in the
+// projection's tail); nrms_forward_prepare's has none, so nothing there
+// depends on an id.
+Launched prepare_weights(const ForwardArgs& a, const StepLaunchPlan& p, hipStream_t stream) {
+  const WeightRows nwr = qkv_rows(a.news_w), uwr = qkv_rows(a.user_w);
+  const bool h3 = p.arith == NRMS_GEMM_SPLIT_F16X3;
+  if (p.prepacked) {
+    if (int32_t st = launch_forward_pack(nwr, p.wt.pack, uwr, p.wt.upack, a.news_w->w_add, p.wt.nwap, h3,
+                                         a.user_w->w_add, p.wt.uwap, stream, p.split_cls ? &p.cjob : nullptr,
+                                         reinterpret_cast<int32_t*>(p.step_ws)))
+      return st;
+  } else if (p.packed) {
+    if (int32_t st = launch_proj_x6_pack(nwr, p.wt.pack, &uwr, p.wt.upack, h3, stream)) return st;
   }
-  if (B == 0) return NRMS_OK;
-  if (!cand_ids || !clicked_ids || !logits || (!table && !(prepared && folded))) return NRMS_ERR_INVALID_ARG;
+  if (!p.folded) return NRMS_OK;
+  return project_qkv({a.table, a.V, contiguous_rows(p.D), nullptr, a.V}, a.news_w, p.wt.table, p.ld, stream,
+                     {.pack = p.wt.pack,
+                      .packed = p.packed,
+                      .arith = p.arith,
+                      .tail = p.classify_tail ? &p.ntail : nullptr});
+}
+
+// Host only: no HIP call, no launch.
+int32_t plan_forward_step(const ForwardArgs& a, StepLaunchPlan* plan) {
+  StepLaunchPlan& p = *plan;
+  const nrms_encoder_weights_t *nw = a.news_w, *uw = a.user_w;
+  if (a.B < 0 || a.C < 0 || a.N <= 0 || a.L <= 0) return NRMS_ERR_INVALID_ARG;
+  if (int32_t st = encoders_ok(a.V, nw, uw)) return st;
+  const int D = p.D = nw->d_model;
+  p.n_clk = a.B * a.N;
+  p.n_all = a.B * (a.C + a.N);
+  p.folded = use_folded(a.proj_mode, p.n_all * a.L, a.V);
+  p.arith = gemm_arith();
+  p.packed = qkv_packs(p.arith, nw);
+  // what is ready before the step (NRMS_STATE_*), and where
+  p.fill_weights = !a.prepared;
+  WeightState sw{};
+  uint32_t have = 0;
+  if (a.prepared) {
+    const nrms_forward_state_t* state = a.state;
+    if (!state || !state->buffer || state->V != a.V || state->D != D || state->gemm_arith != p.arith)
+      return NRMS_ERR_INVALID_ARG;
+    have = state->flags;
+    if (p.folded && !(have & NRMS_STATE_FOLDED_TABLE)) return NRMS_ERR_INVALID_ARG;
+    if (state->ld_qkv != qkv_row_stride(D)) return NRMS_ERR_INVALID_ARG;
+    Carve sc = Carve::over(state->buffer, state->bytes);
+    sw = state_layout(sc, a.V, D, (have & NRMS_STATE_FOLDED_TABLE) != 0);
+    if (!sc.ok) return NRMS_ERR_WORKSPACE;
+  } else {
+    // (the step's own first launches: the fused news tail takes folded + L = 20)
+    have = (p.packed ? NRMS_STATE_QKV_PACKS : 0) | (p.folded ? NRMS_STATE_FOLDED_TABLE | NRMS_STATE_ADD_PACKS : 0);
+  }
+  p.empty = a.B == 0;
+  if (p.empty) return NRMS_OK;
   // (the prepared folded table lives in the state: the workspace has no rows then)
-  const NewsSizes z = news_sizes(n_all, L, V, D, folded);
-  const int64_t ld = (prepared && folded) ? state->ld_qkv : news_ld(news_w, L);
-  const int64_t uld = user_ld(user_w, N);
-  Carve cv{static_cast<char*>(workspace), workspace ? workspace_bytes : 0};
-  float* qkv = (prepared && folded) ? sw.table : cv.floats(z.qkv);
-  float* ctx = cv.floats(z.ctx);
-  float* scores = cv.floats(z.scores);
-  float* wap = cv.floats(z.wap);
-  float* pack = cv.floats(z.pack);
-  float* news = cv.floats((size_t)n_all * D);   // [clicked B*N | candidates B*C] x D
-  float* user = cv.floats((size_t)B * D);
-  float* uqkv = cv.floats((size_t)n_clk * (size_t)uld);
-  float* uctx = cv.floats((size_t)n_clk * D);
-  float* uscores = cv.floats((size_t)n_clk);
-  float* uwap = cv.floats(fused_user_packed_b_floats());
-  float* upack = cv.floats(proj_x6_pack_floats());
-  int64_t* ulist = reinterpret_cast<int64_t*>(cv.floats((size_t)n_clk * 2));
-  int32_t* uorder = reinterpret_cast<int32_t*>(cv.floats((size_t)B));   // user dispatch order
+  const bool state_table = !p.fill_weights && p.folded;
+  if (!a.cand_ids || !a.clicked_ids || !a.logits || (!a.table && !state_table)) return NRMS_ERR_INVALID_ARG;
+  Carve cv = Carve::over(a.workspace, a.workspace_bytes);
+  p.ws = forward_layout(cv, a.B, a.C, a.N, a.L, state_table ? 0 : (p.folded ? a.V : p.n_all * a.L), D);
   if (!cv.ok) return NRMS_ERR_WORKSPACE;
+  // (the state's packs were made under this arithmetic: the Q|K|V packs are
+  // there exactly when this step would make them)
+  if (p.packed != ((have & NRMS_STATE_QKV_PACKS) != 0)) return NRMS_ERR_INVALID_ARG;
+  p.user_fused = fused_user_supported(a.N, D, uw->n_heads, uw->query_dim) && ((uintptr_t)p.ws.user % 16) == 0;
+  p.user_rows_here = p.user_fused && p.arith != NRMS_GEMM_F32;
+  p.prepacked = p.packed && p.user_fused && fused_news_supported(a.L, D, nw->n_heads, nw->query_dim) &&
+                (have & NRMS_STATE_ADD_PACKS) != 0;
+  p.wt = WeightState{nullptr, p.ws.n.pack, p.ws.u.pack, p.ws.n.wap, p.ws.u.wap};
+  if (!p.fill_weights) {
+    // both W_add from the state, or both packed by this step's own launches
+    // into its workspace: a step writes nothing into the state
+    if (p.packed) { p.wt.pack = sw.pack; p.wt.upack = sw.upack; }
+    if (p.prepacked) { p.wt.nwap = sw.nwap; p.wt.uwap = sw.uwap; }
+  }
+  p.qkv = state_table ? sw.table : p.ws.n.qkv;
+  if (p.folded) p.wt.table = p.qkv;
+  p.ld = state_table ? a.state->ld_qkv : news_ld(nw, a.L);
+  p.uld = user_ld(uw, a.N);
+  p.step_ws = p.ws.n.wap + fused_news_packed_floats();
+  p.split_cls = p.prepacked && p.folded &&
+                fused_news_classify_split(p.step_ws, a.clicked_ids, p.n_clk, a.cand_ids, p.n_all, a.V, &p.cjob, &p.ntail.sc);
+  p.classify_tail = p.split_cls && !g_skip_classify_tail;
+  p.user_compact = p.user_fused && token_compaction() && a.N <= 64;
+  p.order_tail = p.user_compact && user_lpt() && a.B * a.N <= INT32_MAX;
+  p.score_fold = p.user_fused && a.C > 0 && ((uintptr_t)(p.ws.news + (size_t)p.n_clk * D) % 16) == 0;
+  return NRMS_OK;
+}
+
+// The launches of a planned step. ev (optional, NRMS_FORWARD_STAGES + 1
+// events): recorded on the stream before each stage and after the last.
+int32_t run_forward_step(const ForwardArgs& a, const StepLaunchPlan& p, hipStream_t stream, hipEvent_t* ev) {
+  const nrms_encoder_weights_t *nw = a.news_w, *uw = a.user_w;
+  const ForwardWs& ws = p.ws;
+  const int D = p.D;
+  const int64_t n_clk = p.n_clk, n_all = p.n_all;
   auto rec = [&](int i) -> int32_t {
     if (ev && hipEventRecord(ev[i], stream) != hipSuccess) return launch_status();
     return NRMS_OK;
   };
-
   int32_t st;
-  bool deduped = false, classified = false;
-  const bool user_fused = fused_user_supported(N, D, user_w->n_heads, user_w->query_dim) &&
-                          ((uintptr_t)user % 16) == 0;
-  // with the UserEncoder's row-list projection the clicked padding titles'
-  // vectors are never read, and the scorer reads a copied candidate from the
-  // rep group: no copies are written
-  const int64_t bcast_from = (user_fused && arith != NRMS_GEMM_F32) ? n_all : 0;
-  // ... and the news kernel lists the UserEncoder's rows in its prologue
-  const bool user_rows_here = user_fused && arith != NRMS_GEMM_F32;
-  // every weight split / packing in one launch: both encoders' Q|K|V, and
-  // (fused tails) both W_add
-  const bool packed = arith != NRMS_GEMM_F32 && proj_x6_supported(D, 3 * D, qkv_rows(news_w));
-  const bool news_fused_ok = fused_news_supported(L, D, news_w->n_heads, news_w->query_dim);
-  bool prepacked;
-  if (prepared) {
-    // (the state's packs were made under this arithmetic: the Q|K|V packs are
-    // there exactly when this step would make them)
-    if (packed != ((state->flags & NRMS_STATE_QKV_PACKS) != 0)) return NRMS_ERR_INVALID_ARG;
-    if (packed) { pack = sw.pack; upack = sw.upack; }
-    // both W_add from the state, or both packed by this step's own launches
-    // into its workspace: a step writes nothing into the state
-    prepacked = packed && user_fused && news_fused_ok && (state->flags & NRMS_STATE_ADD_PACKS) != 0;
-    if (prepacked) { uwap = sw.uwap; }
-  } else {
-    const bool all_packed = packed && folded && user_fused;   // (the fused news tail takes folded + L = 20)
-    prepacked = all_packed && news_fused_ok;
-  }
   if ((st = rec(0))) return st;
-  // the news launch's weights (read-only when prepacked) and its own part
-  float* nwap = (prepared && prepacked) ? sw.nwap : wap;
-  float* step_ws = wap + fused_news_packed_floats();
-  // the titles' classification without the atomics (titles.hpp): the first
-  // half in the pack launch and the second in the vocabulary projection's
-  // tail, or (prepared: neither is part of the step) in two launches of its own
-  tl::ClassifyJob cjob{};
-  tl::TailJobs ntail{};
-  const bool split_cls = g_split_classify && prepacked && folded &&
-                         fused_news_classify_split(step_ws, clicked_ids, n_clk, cand_ids, n_all, V, &cjob, &ntail.sc);
   bool tail_done = false;
-  if (prepared) {
-    if (prepacked) {
-      int32_t* counters = reinterpret_cast<int32_t*>(step_ws);
-      if ((st = launch_forward_classify(split_cls ? &cjob : nullptr, counters, stream))) return st;
-      if (split_cls && !g_skip_classify_tail) {
-        if ((st = launch_forward_scatter(ntail.sc, stream))) return st;
-        tail_done = true;
-      }
+  if (p.fill_weights) {
+    const Launched w = prepare_weights(a, p, stream);
+    if (w.st) return w.st;
+    tail_done = w.tail_done;
+  } else if (p.prepacked) {
+    if ((st = launch_forward_classify(p.split_cls ? &p.cjob : nullptr, reinterpret_cast<int32_t*>(p.step_ws), stream)))
+      return st;
+    if (p.classify_tail) {
+      if ((st = launch_forward_scatter(p.ntail.sc, stream))) return st;
+      tail_done = true;
     }
-  } else {
-    const WeightState own{folded ? qkv : nullptr, pack, upack, wap, uwap};
-    st = prepare_weights(table, V, news_w, user_w, arith, packed, prepacked, folded, own, ld, stream,
-                         split_cls ? &cjob : nullptr, reinterpret_cast<int32_t*>(step_ws),
-                         (split_cls && !g_skip_classify_tail) ? &ntail : nullptr, &tail_done);
-    if (st) return st;
   }
-  if (folded) {
+  EncodeOpts eo{ws.n.ctx, ws.n.scores, p.wt.nwap};   // (W_add: read-only when prepacked)
+  eo.news.prepacked = p.prepacked;
+  eo.news.step_ws = p.step_ws;
+  int64_t n_rows = a.V;
+  if (p.folded) {
     if ((st = rec(1))) return st;
-    // (without the second half the news launch classifies the titles itself)
-    st = encode_from_qkv(qkv, ld, V, clicked_ids, n_clk, cand_ids, n_all, L, news_w, ctx, scores,
-                         news, stream, nwap, &deduped, bcast_from, user_rows_here ? ulist : nullptr, n_clk,
-                         prepacked, false, &classified, split_cls && tail_done, step_ws);
+    eo.news.broadcast_from = p.user_rows_here ? n_all : 0;
+    eo.news.user_list = p.user_rows_here ? ws.ulist : nullptr;
+    eo.news.user_rows = n_clk;
+    eo.news.preclassified = p.split_cls && tail_done;
   } else {
-    st = project_qkv(table, V, contiguous_rows(D), clicked_ids, n_clk * L, news_w, pack, packed, qkv, ld,
-                     stream, nullptr, arith);
-    if (st) return st;
-    st = project_qkv(table, V, contiguous_rows(D), cand_ids, B * C * L, news_w, pack, packed,
-                     qkv + (size_t)n_clk * L * ld, ld, stream, nullptr, arith);
-    if (st) return st;
+    const ProjOpts po{.pack = p.wt.pack, .packed = p.packed, .arith = p.arith};
+    const ARows rows = contiguous_rows(D);
+    if ((st = project_qkv({a.table, a.V, rows, a.clicked_ids, n_clk * a.L}, nw, p.qkv, p.ld, stream, po).st)) return st;
+    if ((st = project_qkv({a.table, a.V, rows, a.cand_ids, a.B * a.C * a.L}, nw, p.qkv + (size_t)n_clk * a.L * p.ld,
+                          p.ld, stream, po)
+                  .st))
+      return st;
     if ((st = rec(1))) return st;
-    // (the ids only classify the tokens: the rows are per token; the all-padding
-    // titles' copies are written for every title, so the UserEncoder and the
-    // scorer read plain rows)
-    st = encode_from_qkv(qkv, ld, n_all * L, clicked_ids, n_clk, cand_ids, n_all, L, news_w, ctx,
-                         scores, news, stream, nwap, nullptr, 0, nullptr, 0, prepacked, /*direct_rows=*/true,
-                         &classified, false, step_ws);
+    // (the ids only classify the tokens: the rows are per token)
+    eo.news.direct_rows = true;
+    n_rows = n_all * a.L;
   }
-  if (st) return st;
+  const Launched nl =
+      encode_from_qkv({p.qkv, p.ld, n_rows}, {a.clicked_ids, n_clk, a.cand_ids, n_all}, a.L, nw, ws.news, stream, eo);
+  if (nl.st) return nl.st;
   if ((st = rec(2))) return st;
+  // (the direct mode has no ids to deduplicate by downstream: the all-padding
+  // titles' copies are written for every title, so the UserEncoder and the
+  // scorer read plain rows)
+  const bool deduped = p.folded && nl.deduped;
   // UserEncoder (src/model/NRMS/user_encoder.py:15-26) over the clicked news
   // vectors. After a deduplicating news launch, the clicked titles of copied
   // all-padding groups have the rep group's vectors (bitwise; not written out
-  // here, see bcast_from), so their q|k|v rows are the rep rows': only the
-  // other rows are projected (row-list GEMM) and the fused tail reads copied
-  // positions from the rep rows. Bitwise the same logits as projecting every row.
-  const bool user_dedupe = deduped && user_fused && arith != NRMS_GEMM_F32;
-  // UserEncoder token compaction (user_fused.hip): a user's padding positions
-  // (one news vector) collapse into one row carrying their count
-  const bool user_compact = user_fused && classified && token_compaction() && N <= 64;
-  PaddingGroups pg{nullptr, nullptr, nullptr};
-  const PaddingGroups pg_all = deduped ? fused_news_padding_groups(step_ws, n_all) : pg;
-  const PaddingGroups pg_flags = classified ? fused_news_padding_groups(step_ws, n_all) : pg;
-  // the users' longest-first dispatch order in the projection's tail (titles.hpp)
+  // here, see user_rows_here), so their q|k|v rows are the rep rows': only the
+  // other rows are projected (row-list GEMM, listed by the news kernel's
+  // prologue) and the fused tail reads copied positions from the rep rows.
+  // Bitwise the same logits as projecting every row.
+  const bool user_dedupe = deduped && p.user_rows_here;
+  const bool user_compact = p.user_compact && nl.classified;
+  const bool order_tail = p.order_tail && user_compact;
+  const PaddingGroups groups = fused_news_padding_groups(p.step_ws, n_all);   // (valid where nl.classified)
   tl::TailJobs utail{};
-  const bool order_tail = g_split_classify && user_compact && user_lpt() && B * N <= INT32_MAX;
-  if (order_tail) utail.uo = tl::UserOrder{pg_flags.pad_title, uorder, B, N};
-  bool order_ready = false;
-  if (user_dedupe) {
-    pg = fused_news_padding_groups(step_ws, n_all);
-    // (listed by the news kernel's prologue in the folded mode; the direct mode
-    // has no ids to deduplicate by, so user_dedupe is false there)
-    st = project_qkv(news, n_clk, contiguous_rows(D), ulist, n_clk, user_w, upack, packed, uqkv, uld, stream,
-                     pg.user_count, arith, order_tail ? &utail : nullptr, &order_ready);
-  } else {
-    st = project_qkv(news, n_clk, contiguous_rows(D), nullptr, n_clk, user_w, upack, packed, uqkv, uld, stream,
-                     nullptr, arith, order_tail ? &utail : nullptr, &order_ready);
-  }
-  if (st) return st;
+  if (order_tail) utail.uo = tl::UserOrder{groups.pad_title, ws.uorder, a.B, a.N};
+  const Launched up = project_qkv({ws.news, n_clk, contiguous_rows(D), user_dedupe ? ws.ulist : nullptr, n_clk}, uw,
+                                  ws.u.qkv, p.uld, stream,
+                                  {.pack = p.wt.upack,
+                                   .packed = p.packed,
+                                   .list_count = user_dedupe ? groups.user_count : nullptr,
+                                   .arith = p.arith,
+                                   .tail = order_tail ? &utail : nullptr});
+  if (up.st) return up.st;
   if ((st = rec(3))) return st;
-  // the click scores in the fused UserEncoder launch (bitwise the score
-  // kernel's; its stage is then empty)
-  const float* cand_news = news + (size_t)n_clk * D;
-  const PaddingGroups* cand_pg = bcast_from == n_all && deduped ? &pg_all : nullptr;
-  const bool score_fold = g_score_fold && user_fused && C > 0 && ((uintptr_t)cand_news % 16) == 0;
-  const ScoreFold sfold{cand_news, logits, cand_pg ? *cand_pg : PaddingGroups{nullptr, nullptr, nullptr}, n_clk, C};
-  if (user_fused)
-    st = launch_fused_user(uqkv, uld, B, N, user_w->w_add, user_w->b_add, user_w->q_add, uwap, user,
-                           stream, (user_dedupe || user_compact) ? &pg_flags : nullptr, prepacked, user_dedupe,
-                           user_compact, uorder, order_ready, score_fold ? &sfold : nullptr);
+  const float* cand_news = ws.news + (size_t)n_clk * D;
+  const PaddingGroups none{nullptr, nullptr, nullptr};
+  const ScoreFold sfold{cand_news, a.logits, user_dedupe ? groups : none, n_clk, a.C};
+  if (p.user_fused)
+    st = launch_fused_user({ws.u.qkv, p.uld}, a.B, a.N, additive(uw), p.wt.uwap, ws.user, stream,
+                           {.pg = (user_dedupe || user_compact) ? &groups : nullptr,
+                            .prepacked = p.prepacked,
+                            .copied = user_dedupe,
+                            .compact = user_compact,
+                            .order = ws.uorder,
+                            .order_ready = up.tail_done,
+                            .score = p.score_fold ? &sfold : nullptr});
   else
-    st = encode_from_qkv(uqkv, uld, n_clk, nullptr, B, nullptr, B, N, user_w, uctx, uscores, user,
-                         stream);
+    st = encode_from_qkv({ws.u.qkv, p.uld, n_clk}, {nullptr, a.B, nullptr, a.B}, a.N, uw, ws.user, stream,
+                         {ws.u.ctx, ws.u.scores})
+             .st;
   if (st) return st;
   if ((st = rec(4))) return st;
-  if (!score_fold) {
-    st = launch_score(cand_news, B, C, (int64_t)C * D, D, user, D, D, logits, stream, cand_pg, n_clk);
+  if (!p.score_fold) {
+    st = launch_score(cand_news, a.B, a.C, (int64_t)a.C * D, D, ws.user, D, D, a.logits, stream);
     if (st) return st;
   }
   return rec(5);
 }
 
+int32_t forward_step(const ForwardArgs& a, hipStream_t stream, hipEvent_t* ev) {
+  StepLaunchPlan p{};
+  if (int32_t st = plan_forward_step(a, &p)) return st;
+  return p.empty ? NRMS_OK : run_forward_step(a, p, stream, ev);
+}
+
 }  // namespace
+
+extern "C" {
 
 int32_t nrms_forward(const int64_t* cand_ids, const int64_t* clicked_ids, int64_t B, int32_t C,
                      int32_t N, int32_t L, const float* table, int64_t V,
                      const nrms_encoder_weights_t* news_w, const nrms_encoder_weights_t* user_w,
                      int32_t proj_mode, float* logits, void* workspace, size_t workspace_bytes,
                      hipStream_t stream) {
-  return forward_impl(cand_ids, clicked_ids, B, C, N, L, table, V, news_w, user_w, proj_mode, logits,
-                      workspace, workspace_bytes, stream, nullptr, nullptr, false);
+  return forward_step({cand_ids, clicked_ids, B, C, N, L, table, V, news_w, user_w, proj_mode, logits, workspace,
+                       workspace_bytes, nullptr, false},
+                      stream, nullptr);
 }
 
 int32_t nrms_forward_prepare(const float* table, int64_t V, const nrms_encoder_weights_t* news_w,
@@ -814,44 +907,42 @@ int32_t nrms_forward_prepare(const float* table, int64_t V, const nrms_encoder_w
                              size_t state_bytes, nrms_forward_state_t* state, hipStream_t stream) {
   if (!state) return NRMS_ERR_INVALID_ARG;
   *state = nrms_forward_state_t{};   // (unusable until this call succeeds)
-  if (V <= 0 || !table) return NRMS_ERR_INVALID_ARG;
-  if (int32_t st = shape_ok(news_w)) return st;
-  if (int32_t st = shape_ok(user_w)) return st;
-  if (news_w->d_model != user_w->d_model) return NRMS_ERR_INVALID_ARG;
-  const int D = news_w->d_model;
-  const bool with_table = with_folded_table != 0;
-  WeightState sw{};
-  if (!state_buf || state_bytes < nrms_forward_state_size(V, D, with_table) ||
-      !carve_state(state_buf, state_bytes, V, D, with_table, &sw))
-    return NRMS_ERR_WORKSPACE;
-  const int arith = gemm_arith();
-  const bool packed = arith != NRMS_GEMM_F32 && proj_x6_supported(D, 3 * D, qkv_rows(news_w));
+  if (!table) return NRMS_ERR_INVALID_ARG;
+  if (int32_t st = encoders_ok(V, news_w, user_w)) return st;
+  // the weight phase of a step with no ids: a plan of its own
+  ForwardArgs a{};
+  a.table = table, a.V = V, a.news_w = news_w, a.user_w = user_w;
+  StepLaunchPlan p{};
+  const int D = p.D = news_w->d_model;
+  p.folded = with_folded_table != 0;
+  Carve cv = Carve::over(state_buf, state_bytes);
+  p.wt = state_layout(cv, V, D, p.folded);
+  if (!cv.ok) return NRMS_ERR_WORKSPACE;
+  p.arith = gemm_arith();
+  p.packed = qkv_packs(p.arith, news_w);
   // (the W_add packs are those of the fused tails: any title length / history
   // length they take has the same packs)
-  const bool add_packs = packed && fused_news_supported(tl::FL, D, news_w->n_heads, news_w->query_dim) &&
-                         fused_user_supported(1, D, user_w->n_heads, user_w->query_dim);
-  const int64_t ld = qkv_row_stride(D);
-  if (int32_t st = prepare_weights(table, V, news_w, user_w, arith, packed, add_packs, with_table, sw, ld, stream))
-    return st;
+  p.prepacked = p.packed && fused_news_supported(tl::FL, D, news_w->n_heads, news_w->query_dim) &&
+                fused_user_supported(1, D, user_w->n_heads, user_w->query_dim);
+  p.ld = qkv_row_stride(D);
+  if (int32_t st = prepare_weights(a, p, stream).st) return st;
   state->buffer = state_buf;
   state->bytes = state_bytes;
   state->V = V;
   state->D = D;
-  state->ld_qkv = (int32_t)ld;
-  state->gemm_arith = arith;
-  state->flags = (with_table ? NRMS_STATE_FOLDED_TABLE : 0) | (packed ? NRMS_STATE_QKV_PACKS : 0) |
-                 (add_packs ? NRMS_STATE_ADD_PACKS : 0);
+  state->ld_qkv = (int32_t)p.ld;
+  state->gemm_arith = p.arith;
+  state->flags = (p.folded ? NRMS_STATE_FOLDED_TABLE : 0) | (p.packed ? NRMS_STATE_QKV_PACKS : 0) |
+                 (p.prepacked ? NRMS_STATE_ADD_PACKS : 0);
   return NRMS_OK;
 }
 
 size_t nrms_forward_prepared_workspace_size(int64_t B, int32_t C, int32_t N, int32_t L, int32_t D) {
-  return nrms_forward_workspace_size(B, C, N, L, 0, D, NRMS_PROJ_DIRECT);
+  return forward_bytes(B, C, N, L, B * (C + N) * L, D);
 }
 
 size_t nrms_forward_prepared_folded_workspace_size(int64_t B, int32_t C, int32_t N, int32_t L, int32_t D) {
-  const size_t all = nrms_forward_prepared_workspace_size(B, C, N, L, D);
-  if (all == 0) return 0;
-  return all - align_up((size_t)B * (size_t)(C + N) * (size_t)L * (size_t)qkv_row_stride(D) * 4);
+  return forward_bytes(B, C, N, L, 0, D);
 }
 
 int32_t nrms_forward_prepared(const int64_t* cand_ids, const int64_t* clicked_ids, int64_t B, int32_t C,
@@ -859,8 +950,9 @@ int32_t nrms_forward_prepared(const int64_t* cand_ids, const int64_t* clicked_id
                               const nrms_encoder_weights_t* news_w, const nrms_encoder_weights_t* user_w,
                               int32_t proj_mode, float* logits, void* workspace, size_t workspace_bytes,
                               hipStream_t stream, const nrms_forward_state_t* state) {
-  return forward_impl(cand_ids, clicked_ids, B, C, N, L, table, V, news_w, user_w, proj_mode, logits,
-                      workspace, workspace_bytes, stream, nullptr, state, true);
+  return forward_step({cand_ids, clicked_ids, B, C, N, L, table, V, news_w, user_w, proj_mode, logits, workspace,
+                       workspace_bytes, state, true},
+                      stream, nullptr);
 }
 
 int32_t nrms_forward_prepared_timed(const int64_t* cand_ids, const int64_t* clicked_ids, int64_t B, int32_t C,
@@ -871,8 +963,9 @@ int32_t nrms_forward_prepared_timed(const int64_t* cand_ids, const int64_t* clic
                                     hipEvent_t* stage_events, int32_t n_events) {
   if (n_events != 0 && (n_events != NRMS_FORWARD_STAGES + 1 || !stage_events))
     return NRMS_ERR_INVALID_ARG;
-  return forward_impl(cand_ids, clicked_ids, B, C, N, L, table, V, news_w, user_w, proj_mode, logits,
-                      workspace, workspace_bytes, stream, n_events ? stage_events : nullptr, state, true);
+  return forward_step({cand_ids, clicked_ids, B, C, N, L, table, V, news_w, user_w, proj_mode, logits, workspace,
+                       workspace_bytes, state, true},
+                      stream, n_events ? stage_events : nullptr);
 }
 
 int32_t nrms_forward_timed(const int64_t* cand_ids, const int64_t* clicked_ids, int64_t B, int32_t C,
@@ -882,8 +975,9 @@ int32_t nrms_forward_timed(const int64_t* cand_ids, const int64_t* clicked_ids, 
                            hipStream_t stream, hipEvent_t* stage_events, int32_t n_events) {
   if (n_events != 0 && (n_events != NRMS_FORWARD_STAGES + 1 || !stage_events))
     return NRMS_ERR_INVALID_ARG;
-  return forward_impl(cand_ids, clicked_ids, B, C, N, L, table, V, news_w, user_w, proj_mode, logits,
-                      workspace, workspace_bytes, stream, n_events ? stage_events : nullptr, nullptr, false);
+  return forward_step({cand_ids, clicked_ids, B, C, N, L, table, V, news_w, user_w, proj_mode, logits, workspace,
+                       workspace_bytes, nullptr, false},
+                      stream, n_events ? stage_events : nullptr);
 }
 
 const char* nrms_forward_stage_name(int32_t i) {
@@ -918,8 +1012,7 @@ int32_t nrms_additive_forward_train(const float* x, int64_t n_seq, int32_t L,
 
 size_t nrms_additive_backward_workspace_size(int64_t n_seq, int32_t L, int32_t D, int32_t Q) {
   if (n_seq < 0 || L <= 0 || D <= 0 || Q <= 0) return 0;
-  return align_up((size_t)n_seq * L * Q * 4) + align_up((size_t)D * Q * 4) +
-         align_up(additive_backward_part_floats(n_seq, Q) * 4) + align_up(gemm_tn_part_floats(Q, D) * 4);
+  return measure([&](Carve& cv) { additive_backward_layout(cv, n_seq, L, D, Q); });
 }
 
 int32_t nrms_additive_backward(const float* x, int64_t n_seq, int32_t L,
@@ -934,27 +1027,19 @@ int32_t nrms_additive_backward(const float* x, int64_t n_seq, int32_t L,
     return NRMS_ERR_INVALID_ARG;
   const int D = w->d_model, Q = w->query_dim;
   if (D % 4 != 0 || Q % 4 != 0) return NRMS_ERR_UNSUPPORTED;
-  Carve cv{static_cast<char*>(workspace), workspace ? workspace_bytes : 0};
-  float* dz = cv.floats((size_t)n_seq * L * Q);
-  float* waT = cv.floats((size_t)D * Q);
-  float* part_rows = cv.floats(additive_backward_part_floats(n_seq, Q));
-  float* part_tn = cv.floats(gemm_tn_part_floats(Q, D));
+  Carve cv = Carve::over(workspace, workspace_bytes);
+  const AdditiveBackwardWs z = additive_backward_layout(cv, n_seq, L, D, Q);
   if (!cv.ok) return NRMS_ERR_WORKSPACE;
+  float *dz = z.dz, *waT = z.waT;
   int32_t st = launch_additive_backward_rows(x, y_tanh, scores, w->q_add, dout, n_seq, L, D, Q, dx,
-                                             dz, d_q_add, d_b_add, part_rows, stream);
+                                             dz, d_q_add, d_b_add, z.part_rows, stream);
   if (st) return st;
   const float* wa[1] = {w->w_add};
   st = launch_transpose(wa, 1, Q, D, waT, stream);   // [Q, D] -> [D, Q]
   if (st) return st;
-  WeightRows r{};
-  r.w[0] = waT;
-  r.b[0] = nullptr;
-  r.seg_rows = D;
-  r.nseg = 1;
-  r.accumulate = 1;
-  st = launch_gemm_store_f32(dz, n_seq * L, Q, r, D, dx, D, stream);   // dx += dz W_add
+  st = launch_gemm_store_f32(dz, n_seq * L, Q, one_segment(waT, D, 1), D, dx, D, stream);   // dx += dz W_add
   if (st) return st;
-  return launch_gemm_tn(dz, n_seq * L, Q, x, D, d_w_add, nullptr, part_tn, stream);   // dW += dz^T x
+  return launch_gemm_tn(dz, n_seq * L, Q, x, D, d_w_add, nullptr, z.part_tn, stream);   // dW += dz^T x
 }
 
 int32_t nrms_self_attention_backward(const float* qkv, const float* dctx, int64_t n_seq,
@@ -969,7 +1054,7 @@ int32_t nrms_self_attention_backward(const float* qkv, const float* dctx, int64_
 
 size_t nrms_qkv_project_backward_workspace_size(int32_t D) {
   if (D <= 0) return 0;
-  return align_up((size_t)3 * D * D * 4) + align_up(gemm_tn_part_floats(3 * D, D) * 4);
+  return measure([&](Carve& cv) { project_backward_layout(cv, D); });
 }
 
 int32_t nrms_qkv_project_backward(const float* x, int64_t rows, const nrms_encoder_weights_t* w,
@@ -981,23 +1066,17 @@ int32_t nrms_qkv_project_backward(const float* x, int64_t rows, const nrms_encod
   if (!x || !dqkv || !d_w_qkv || !d_b_qkv) return NRMS_ERR_INVALID_ARG;
   const int D = w->d_model;
   int32_t st;
-  Carve cv{static_cast<char*>(workspace), workspace ? workspace_bytes : 0};
-  float* wT = cv.floats((size_t)3 * D * D);
-  float* part_tn = cv.floats(gemm_tn_part_floats(3 * D, D));
+  Carve cv = Carve::over(workspace, workspace_bytes);
+  const ProjectBackwardWs z = project_backward_layout(cv, D);
   if (!cv.ok) return NRMS_ERR_WORKSPACE;
   if (dx) {
     const float* ws3[3] = {w->w_q, w->w_k, w->w_v};
-    st = launch_transpose(ws3, 3, D, D, wT, stream);   // [3D, D] -> [D, 3D]
+    st = launch_transpose(ws3, 3, D, D, z.wT, stream);   // [3D, D] -> [D, 3D]
     if (st) return st;
-    WeightRows r{};
-    r.w[0] = wT;
-    r.b[0] = nullptr;
-    r.seg_rows = D;
-    r.nseg = 1;
-    st = launch_gemm_store_f32(dqkv, rows, 3 * D, r, D, dx, D, stream);   // dx = dqkv [Wq; Wk; Wv]
+    st = launch_gemm_store_f32(dqkv, rows, 3 * D, one_segment(z.wT, D, 0), D, dx, D, stream);   // dx = dqkv [Wq; Wk; Wv]
     if (st) return st;
   }
-  return launch_gemm_tn(dqkv, rows, 3 * D, x, D, d_w_qkv, d_b_qkv, part_tn, stream);
+  return launch_gemm_tn(dqkv, rows, 3 * D, x, D, d_w_qkv, d_b_qkv, z.part_tn, stream);
 }
 
 int32_t nrms_score_backward(const float* news, int64_t B, int32_t C, int64_t stride_b,

@@ -1426,17 +1426,12 @@ bool fused_news_classify_split(float* step_ws, const int64_t* ids_a, int64_t n_s
   return true;
 }
 
-int32_t launch_fused_news(const float* qkv, int64_t ldq, int64_t n_rows, const int64_t* ids_a,
-                          int64_t n_seq_a, const int64_t* ids_b, int64_t n_titles,
-                          const float* w_add, const float* b_add, const float* q_add, float* ws,
-                          float* out, hipStream_t s, int dedupe_setting, bool* deduped,
-                          int64_t broadcast_from, int64_t* user_list, int64_t user_rows, bool prepacked,
-                          bool direct_rows, int compact_setting, bool* classified, bool preclassified,
-                          float* step_ws) {
-  if (deduped) *deduped = false;
-  if (classified) *classified = false;
+Launched launch_fused_news(const QkvRows& rows, const TitleIds& ids, const AdditiveWeights& aw, float* ws, float* out,
+                           hipStream_t s, const FusedNewsOpts& o) {
+  const float* qkv = rows.p;
+  const int64_t ldq = rows.ld, n_titles = ids.n;
   if (n_titles == 0) return NRMS_OK;
-  if (!step_ws) step_ws = ws + fused_news_list_offset();
+  float* step_ws = o.step_ws ? o.step_ws : ws + fused_news_list_offset();
   if (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)ws | (uintptr_t)step_ws) % 16) return NRMS_ERR_UNSUPPORTED;
   if (ldq < 3 * FD || ldq % 4) return NRMS_ERR_UNSUPPORTED;   // float4 q / k slices
   if (max_groups(n_titles) >= (1ll << 27)) return NRMS_ERR_UNSUPPORTED;   // recheck entries: group << 4 | mask
@@ -1447,7 +1442,7 @@ int32_t launch_fused_news(const float* qkv, int64_t ldq, int64_t n_rows, const i
   const NewsWs z = news_ws(step_ws, n_titles);
   const RecheckList rl{z.counters + CNT_RECHECK, z.recheck};
   const ClassifyDecision cd =
-      classify_decision(ids_a, ids_b, n_titles, n_rows, direct_rows, dedupe_setting, compact_setting);
+      classify_decision(ids.a, ids.b, n_titles, rows.n_rows, o.direct_rows, o.dedupe_setting, o.compact_setting);
   const bool classify = cd.classify, dedupe = cd.dedupe, compact = cd.compact;
   auto kern = classify ? (h3 ? &fused_news_kernel<2, false, true>
                              : (x6 ? &fused_news_kernel<1, false, true> : &fused_news_kernel<0, false, true>))
@@ -1459,26 +1454,26 @@ int32_t launch_fused_news(const float* qkv, int64_t ldq, int64_t n_rows, const i
   const size_t lds_bytes_exact = x6 ? LDS_BYTES_X6 : LDS_BYTES;
   ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds_bytes);
   ensure_dynamic_lds(reinterpret_cast<const void*>(kern_exact), (int)lds_bytes_exact);
-  if (preclassified && (!classify || direct_rows || !prepacked)) return NRMS_ERR_INVALID_ARG;
+  if (o.preclassified && (!classify || o.direct_rows || !o.prepacked)) return NRMS_ERR_INVALID_ARG;
   const TitleSet ts{classify ? z.crow : nullptr, z.cnt, classify ? z.list : nullptr, z.counters, n_titles,
                     compact ? 0 : NBK - 1};
   // the UserEncoder's row list (nrms_forward) in the main pass's prologue
-  const UserRows ur{dedupe && user_list && user_rows > 0 ? user_list : nullptr, user_rows, z.pad_title,
+  const UserRows ur{dedupe && o.user_list && o.user_rows > 0 ? o.user_list : nullptr, o.user_rows, z.pad_title,
                     z.counters + CNT_REP, z.counters + CNT_USER};
-  if (prepacked) {
+  if (o.prepacked) {
     // (forward_pack_kernel packed W_add and reset the counters; the prepared
     // step: nrms_forward_prepare packed, forward_classify_kernel reset)
   } else if (x6) {
     const int npk = XKS * FNT * 64 * 8 + SPECIAL_FLOATS;
     if (h3)
-      hipLaunchKernelGGL(pack_additive_b3_kernel<true>, dim3((npk + 255) / 256), dim3(256), 0, s, w_add, ws,
+      hipLaunchKernelGGL(pack_additive_b3_kernel<true>, dim3((npk + 255) / 256), dim3(256), 0, s, aw.w, ws,
                          z.counters);
     else
-      hipLaunchKernelGGL(pack_additive_b3_kernel<false>, dim3((npk + 255) / 256), dim3(256), 0, s, w_add, ws,
+      hipLaunchKernelGGL(pack_additive_b3_kernel<false>, dim3((npk + 255) / 256), dim3(256), 0, s, aw.w, ws,
                          z.counters);
   } else {
     const int npk = WAP_FLOATS + SPECIAL_FLOATS;
-    hipLaunchKernelGGL(pack_additive_b_kernel, dim3((npk + 255) / 256), dim3(256), 0, s, w_add, ws,
+    hipLaunchKernelGGL(pack_additive_b_kernel, dim3((npk + 255) / 256), dim3(256), 0, s, aw.w, ws,
                        z.counters);
   }
   if (int32_t st = launch_status()) return st;
@@ -1490,33 +1485,35 @@ int32_t launch_fused_news(const float* qkv, int64_t ldq, int64_t n_rows, const i
   }
   const int64_t groups = classify ? max_groups(n_titles) : (n_titles + FT - 1) / FT;
   const int64_t blocks = groups < n_cu ? groups : n_cu;   // persistent: one workgroup per CU
-  const RowMap rm{ids_a, ids_b, n_seq_a, n_titles, n_rows, direct_rows};
-  if (classify && !preclassified) {
+  const RowMap rm{ids.a, ids.b, ids.n_a, n_titles, rows.n_rows, o.direct_rows};
+  if (classify && !o.preclassified) {
     const Titles tt{z.crow, z.cnt, z.pad_title, z.list, z.counters, n_titles};
     hipLaunchKernelGGL(classify_titles_kernel, dim3((unsigned)((n_titles + CLS_T - 1) / CLS_T)), dim3(CLS_T), 0, s,
                        rm, tt, dedupe ? 1 : 0, compact ? 1 : 0);
     if (int32_t st = launch_status()) return st;
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NTHR), lds_bytes, s, qkv, ldq, rm, ts, ws,
-                     b_add, q_add, out, rl, ur NRMS_TIMING_ARG);
+                     aw.b, aw.q, out, rl, ur NRMS_TIMING_ARG);
   if (int32_t st = launch_status()) return st;
   // the recheck pass: reads the count the main pass left; exits at once when 0
   const int64_t blocks_x = blocks < 16 ? blocks : 16;   // (flagged groups are rare; a smaller grid launches faster)
   hipLaunchKernelGGL(kern_exact, dim3((unsigned)blocks_x), dim3(NTHR), lds_bytes_exact, s, qkv, ldq, rm, ts,
-                     ws, b_add, q_add, out, rl, UserRows{nullptr, 0, nullptr, nullptr, nullptr} NRMS_TIMING_ARG);
+                     ws, aw.b, aw.q, out, rl, UserRows{nullptr, 0, nullptr, nullptr, nullptr} NRMS_TIMING_ARG);
   if (int32_t st = launch_status()) return st;
   // (titles below broadcast_from are not copied: nrms_forward's UserEncoder
   // reads the clicked padding titles from the rep title's rows)
-  const int64_t b0 = broadcast_from < 0 ? 0 : broadcast_from;
+  const int64_t b0 = o.broadcast_from < 0 ? 0 : o.broadcast_from;
   if (dedupe && b0 < n_titles) {
     const int64_t nt4 = (n_titles - b0) * (FD / 4);
     hipLaunchKernelGGL(broadcast_padding_kernel, dim3((unsigned)((nt4 + 255) / 256)), dim3(256), 0, s,
                        z.pad_title, z.counters + CNT_REP, b0, n_titles, out);
   }
-  const int32_t st = launch_status();
-  if (st == NRMS_OK && deduped) *deduped = dedupe;
-  if (st == NRMS_OK && classified) *classified = classify;
-  return st;
+  Launched did = launch_status();
+  if (did.st == NRMS_OK) {
+    did.deduped = dedupe;
+    did.classified = classify;
+  }
+  return did;
 }
 
 PaddingGroups fused_news_padding_groups(float* step_ws, int64_t n_titles) {

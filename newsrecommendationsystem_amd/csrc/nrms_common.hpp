@@ -240,6 +240,33 @@ struct ARows {
 };
 inline ARows contiguous_rows(int K) { return ARows{INT64_MAX, 0, K}; }
 
+// Operand tuples the encoder launchers share.
+// q|k|v rows: row stride ld in floats, n_rows rows (0: as many as the ids / the shape address)
+struct QkvRows {
+  const float* p;
+  int64_t ld, n_rows = 0;
+};
+// The token ids of n titles: titles < n_a from a, the others from b (b null:
+// all from a; a null: no ids, title s has rows s L .. s L + L - 1).
+struct TitleIds {
+  const int64_t* a;
+  int64_t n_a;
+  const int64_t* b;
+  int64_t n;
+};
+// additive attention: W_add [Q, D], b_add [Q], q_add [Q]
+struct AdditiveWeights {
+  const float *w, *b, *q;
+};
+// What a launcher did, next to its status (a bare status converts: nothing done).
+struct Launched {
+  Launched(int32_t status = NRMS_OK) : st(status) {}
+  int32_t st;
+  bool deduped = false;      // launch_fused_news deduplicated the all-padding titles
+  bool classified = false;   // ... classified them at all (fused_news_padding_groups' pad_title flags are valid)
+  bool tail_done = false;    // project_qkv ran the tail jobs (the fragment path took them)
+};
+
 // Host-side launchers (defined in the .hip files).
 int32_t launch_gather(const int64_t* ids, int64_t n_tok, const float* table, int64_t V, int D,
                       float* out, hipStream_t s);
@@ -366,11 +393,16 @@ struct ScoreFold {
   int64_t title0;      // title index of candidate 0 (pg)
   int C;
 };
-int32_t launch_fused_user(const float* qkv, int64_t ldq, int64_t B, int L, const float* w_add,
-                          const float* b_add, const float* q_add, float* wap, float* out,
-                          hipStream_t s, const PaddingGroups* pg = nullptr, bool prepacked = false,
-                          bool copied = false, bool compact = false, int32_t* order = nullptr,
-                          bool order_ready = false, const ScoreFold* score = nullptr);
+struct FusedUserOpts {
+  const PaddingGroups* pg = nullptr;
+  bool prepacked = false;   // wap already holds the packed W_add (launch_forward_pack)
+  bool copied = false, compact = false;
+  int32_t* order = nullptr;
+  bool order_ready = false;   // order was computed by the UserEncoder projection's tail (titles.hpp)
+  const ScoreFold* score = nullptr;
+};
+int32_t launch_fused_user(const QkvRows& qkv, int64_t B, int L, const AdditiveWeights& aw, float* wap, float* out,
+                          hipStream_t s, const FusedUserOpts& o = {});
 // the longest-first user dispatch order is on (NRMS_USER_LPT, default 1)
 bool user_lpt();
 // Process-wide switch (news_fused.hip): encode one all-padding title per
@@ -396,11 +428,7 @@ size_t fused_news_workspace_floats(int64_t n_titles);
 size_t fused_news_packed_floats();
 bool fused_news_supported(int L, int D, int H, int Q);
 // dedupe_setting / compact_setting: -1 = the process-wide setting
-// (nrms_set_title_dedupe / nrms_set_token_compaction), else 0 / 1; *deduped
-// (optional) tells whether the launch deduplicated the all-padding titles;
-// *classified (optional) whether it classified them at all (the pad_title
-// flags of fused_news_padding_groups are then valid until the workspace is
-// reused).
+// (nrms_set_title_dedupe / nrms_set_token_compaction), else 0 / 1.
 // broadcast_from: the copies of the rep title's vector are written for titles
 // >= broadcast_from only. user_list (optional): when the launch deduplicates,
 // the main pass also builds launch_user_row_list's list of titles
@@ -411,16 +439,42 @@ bool fused_news_supported(int L, int D, int H, int Q);
 // launch here.
 // direct_rows: the q|k|v rows are per token (row s L + i, the per-token
 // projection); the ids (if any) only classify the tokens.
-int32_t launch_fused_news(const float* qkv, int64_t ldq, int64_t n_rows, const int64_t* ids_a,
-                          int64_t n_seq_a, const int64_t* ids_b, int64_t n_titles,
-                          const float* w_add, const float* b_add, const float* q_add, float* ws,
-                          float* out, hipStream_t s, int dedupe_setting = -1, bool* deduped = nullptr,
-                          int64_t broadcast_from = 0, int64_t* user_list = nullptr, int64_t user_rows = 0,
-                          bool prepacked = false, bool direct_rows = false, int compact_setting = -1,
-                          bool* classified = nullptr, bool preclassified = false, float* step_ws = nullptr);
+struct FusedNewsOpts {
+  int dedupe_setting = -1, compact_setting = -1;
+  int64_t broadcast_from = 0;
+  int64_t* user_list = nullptr;
+  int64_t user_rows = 0;
+  bool prepacked = false, direct_rows = false, preclassified = false;
+  float* step_ws = nullptr;
+};
+Launched launch_fused_news(const QkvRows& qkv, const TitleIds& ids, const AdditiveWeights& aw, float* ws, float* out,
+                           hipStream_t s, const FusedNewsOpts& o = {});
 // step_ws: the launch's own part of the workspace (null: ws +
 // fused_news_packed_floats()), 16-B aligned
 PaddingGroups fused_news_padding_groups(float* step_ws, int64_t n_titles);
+// encode_from_qkv (capi.hip): attention + additive pooling from projected
+// rows. ctx [n L][D] / scores [n L]: the stage kernels' buffers; wap non-null:
+// the fused news kernel (with `news`) when the geometry allows.
+struct EncodeOpts {
+  float *ctx = nullptr, *scores = nullptr, *wap = nullptr;
+  FusedNewsOpts news;
+};
+// project_qkv (capi.hip). The input: X [n_rows_x] addressed through ar, of
+// which the M rows row_ids lists (null: rows 0 .. M - 1) are projected.
+struct ProjRows {
+  const float* X;
+  int64_t n_rows_x;
+  ARows ar;
+  const int64_t* row_ids;
+  int64_t M;
+};
+struct ProjOpts {
+  float* pack = nullptr;     // proj_x6_pack_floats (null: the staged GEMM)
+  bool packed = false;       // the caller already packed w there, under the same arith
+  const int32_t* list_count = nullptr;   // non-null: row-list mode (launch_gemm_store_list)
+  int arith = -1;            // < 0: the current mode
+  const tl::TailJobs* tail = nullptr;
+};
 // The rows m < n_rows of titles not copied from rep (the UserEncoder's rows to
 // project), appended to list in any order; their count in *pg.user_count.
 int32_t launch_user_row_list(const PaddingGroups& pg, int64_t n_rows, int64_t* list, hipStream_t s);
@@ -443,11 +497,7 @@ int32_t launch_rank_impressions(const float* news, int64_t n_news, const float* 
                                 const int64_t* news_idx, const int64_t* imp_user, const int64_t* offsets,
                                 int64_t n_imp, int D, int tie_mode, float* out_score, int32_t* out_rank,
                                 hipStream_t s);
-// pg (optional): candidates that are copied all-padding titles read the rep
-// title's vector; the candidates are titles title0 + b C + c of a contiguous array
-// (news points at title0's row).
 int32_t launch_score(const float* news, int64_t B, int C, int64_t sb, int64_t sc,
-                     const float* user, int64_t su, int D, float* out, hipStream_t s,
-                     const PaddingGroups* pg = nullptr, int64_t title0 = 0);
+                     const float* user, int64_t su, int D, float* out, hipStream_t s);
 
 }  // namespace nrms

@@ -1056,46 +1056,45 @@ bool fused_user_supported(int L, int D, int H, int Q) {
   return L >= 1 && L <= 64 && D == UD && H == UH && Q == UQ;
 }
 
-int32_t launch_fused_user(const float* qkv, int64_t ldq, int64_t B, int L, const float* w_add,
-                          const float* b_add, const float* q_add, float* wap, float* out,
-                          hipStream_t s, const PaddingGroups* pgp, bool prepacked, bool copied, bool compact,
-                          int32_t* order, bool order_ready, const ScoreFold* score) {
-  const PaddingGroups pg = pgp ? *pgp : PaddingGroups{nullptr, nullptr, nullptr};
-  if (compact && (!pgp || L > 64 || B * L > INT32_MAX)) return NRMS_ERR_UNSUPPORTED;
-  if (copied && !pgp) return NRMS_ERR_INVALID_ARG;
+int32_t launch_fused_user(const QkvRows& rows, int64_t B, int L, const AdditiveWeights& aw, float* wap, float* out,
+                          hipStream_t s, const FusedUserOpts& o) {
+  const bool copied = o.copied, compact = o.compact;
+  const PaddingGroups pg = o.pg ? *o.pg : PaddingGroups{nullptr, nullptr, nullptr};
+  if (compact && (!o.pg || L > 64 || B * L > INT32_MAX)) return NRMS_ERR_UNSUPPORTED;
+  if (copied && !o.pg) return NRMS_ERR_INVALID_ARG;
   const int uflags = (copied ? UF_COPIED : 0) | (compact ? UF_COMPACT : 0) |
                      (g_user_hsplit.load(std::memory_order_relaxed) ? 0 : UF_TASK_SPLIT) |
                      (g_user_pair.load(std::memory_order_relaxed) ? 0 : UF_NO_PAIR);
   if (B == 0) return NRMS_OK;
   if (!fused_user_supported(L, UD, UH, UQ) || B > INT32_MAX) return NRMS_ERR_UNSUPPORTED;
-  if (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)wap) % 16 || ldq < 3 * UD || ldq % 4)
+  if (((uintptr_t)rows.p | (uintptr_t)out | (uintptr_t)wap) % 16 || rows.ld < 3 * UD || rows.ld % 4)
     return NRMS_ERR_UNSUPPORTED;
   ScoreFold sf{};
-  if (score && score->C > 0) {
-    if (!score->news || !score->logits || ((uintptr_t)score->news % 16)) return NRMS_ERR_INVALID_ARG;
-    if (score->pg.pad_title && !score->pg.rep) return NRMS_ERR_INVALID_ARG;
-    sf = *score;
+  if (o.score && o.score->C > 0) {
+    if (!o.score->news || !o.score->logits || ((uintptr_t)o.score->news % 16)) return NRMS_ERR_INVALID_ARG;
+    if (o.score->pg.pad_title && !o.score->pg.rep) return NRMS_ERR_INVALID_ARG;
+    sf = *o.score;
   }
   const int ar = gemm_arith();
   const int mode = ar == NRMS_GEMM_F32 ? 0 : (ar == NRMS_GEMM_SPLIT_F16X3 ? 2 : 1);
-  if (!prepacked) {
+  if (!o.prepacked) {
     const int blocks = mode == 2 ? pk::USER_H3_BLOCKS : ((mode ? UKS * UNT * 64 * 8 : UWAP1) + 255) / 256;
-    hipLaunchKernelGGL(pack_user_b_kernel, dim3(blocks), dim3(256), 0, s, w_add, wap, mode);
+    hipLaunchKernelGGL(pack_user_b_kernel, dim3(blocks), dim3(256), 0, s, aw.w, wap, mode);
     if (int32_t st = launch_status()) return st;
   }
   // longest users first (compaction only: Le comes from the padding flags)
   const int32_t* ord = nullptr;
-  if (compact && order && order_ready) {
-    ord = order;   // (computed by the UserEncoder projection's tail, titles.hpp)
-  } else if (compact && order && g_user_lpt.load(std::memory_order_relaxed)) {
+  if (compact && o.order && o.order_ready) {
+    ord = o.order;   // (computed by the UserEncoder projection's tail, titles.hpp)
+  } else if (compact && o.order && g_user_lpt.load(std::memory_order_relaxed)) {
     hipLaunchKernelGGL(user_order_kernel, dim3((unsigned)((B + UORD_T - 1) / UORD_T)), dim3(UORD_T), 0, s,
-                       pg.pad_title, B, L, order);
+                       pg.pad_title, B, L, o.order);
     if (int32_t st = launch_status()) return st;
-    ord = order;
+    ord = o.order;
   }
-  if (mode == 2) return launch_user_mode<2>(qkv, ldq, B, L, wap, b_add, q_add, out, s, pg, uflags, ord, sf);
-  if (mode == 1) return launch_user_mode<1>(qkv, ldq, B, L, wap, b_add, q_add, out, s, pg, uflags, ord, sf);
-  return launch_user_mode<0>(qkv, ldq, B, L, wap, b_add, q_add, out, s, pg, uflags, ord, sf);
+  if (mode == 2) return launch_user_mode<2>(rows.p, rows.ld, B, L, wap, aw.b, aw.q, out, s, pg, uflags, ord, sf);
+  if (mode == 1) return launch_user_mode<1>(rows.p, rows.ld, B, L, wap, aw.b, aw.q, out, s, pg, uflags, ord, sf);
+  return launch_user_mode<0>(rows.p, rows.ld, B, L, wap, aw.b, aw.q, out, s, pg, uflags, ord, sf);
 }
 
 }  // namespace nrms

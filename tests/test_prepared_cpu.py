@@ -67,3 +67,66 @@ def test_prepare_and_prepared_reject_bad_arguments_without_launch():
     assert lib.nrms_forward_prepared(*args, None) == N.NRMS_ERR_INVALID_ARG
     assert lib.nrms_forward_prepared(*args, st) == N.NRMS_ERR_INVALID_ARG
     assert lib.nrms_forward_prepared_timed(*args, st, None, 3) == N.NRMS_ERR_INVALID_ARG
+
+
+FORWARD_SHAPES = [(1, 1, 1, 20, 1000), (4, 5, 50, 20, 1000), (3, 5, 65, 20, 1000), (5, 2, 7, 5, 1000),
+                  (64, 5, 50, 20, 70976)]
+
+
+def test_every_size_is_tight_against_its_carve():
+    """Each *_workspace_size / nrms_forward_state_size is its call's layout
+    measured: one byte less and the call returns NRMS_ERR_WORKSPACE before it
+    enqueues anything (the GPU suite allocates exactly the reported sizes, which
+    is the other half)."""
+    lib = N.load()
+    D, Q = 300, 200
+    p = ctypes.c_void_p(256)   # (never dereferenced: the carve fails first)
+    w = N.EncoderWeights(*([p.value] * 9), D, 15, Q)
+    ld = lib.nrms_qkv_row_stride(D)
+    short = N.NRMS_ERR_WORKSPACE
+
+    need = lib.nrms_qkv_project_workspace_size(D)
+    assert need > 0 and lib.nrms_qkv_project_ws(p, 7, None, 7, w, p, 0, p, need - 1, None) == short
+    need = lib.nrms_qkv_project_backward_workspace_size(D)
+    assert need > 0 and lib.nrms_qkv_project_backward(p, 7, w, p, p, p, p, p, need - 1, None) == short
+
+    for B, C, Nc, L, V in FORWARD_SHAPES:
+        case = (B, C, Nc, L, V)
+        state_bytes = lib.nrms_forward_state_size(V, D, 1)
+        st = N.ForwardState()
+        assert state_bytes > 0
+        assert lib.nrms_forward_prepare(p, V, w, w, 1, p, state_bytes - 1, st, None) == short, case
+        assert lib.nrms_forward_state_size(V, D, 0) > 0
+        assert lib.nrms_forward_prepare(p, V, w, w, 0, p, lib.nrms_forward_state_size(V, D, 0) - 1, st, None) == short
+        state = N.ForwardState(p.value, state_bytes, V, D, ld, lib.nrms_get_gemm_arith(),
+                               N.NRMS_STATE_FOLDED_TABLE | N.NRMS_STATE_QKV_PACKS | N.NRMS_STATE_ADD_PACKS)
+        for mode in (N.NRMS_PROJ_FOLDED, N.NRMS_PROJ_DIRECT):
+            need = lib.nrms_forward_workspace_size(B, C, Nc, L, V, D, mode)
+            args = (p, p, B, C, Nc, L, p, V, w, w, mode, p, p, need - 1, None)
+            assert need > 0 and lib.nrms_forward(*args) == short, (case, mode)
+            assert lib.nrms_forward_timed(*args, None, 0) == short, (case, mode)
+            need = (lib.nrms_forward_prepared_folded_workspace_size if mode == N.NRMS_PROJ_FOLDED
+                    else lib.nrms_forward_prepared_workspace_size)(B, C, Nc, L, D)
+            args = (p, p, B, C, Nc, L, p, V, w, w, mode, p, p, need - 1, None, state)
+            assert need > 0 and lib.nrms_forward_prepared(*args) == short, (case, mode)
+            assert lib.nrms_forward_prepared_timed(*args, None, 0) == short, (case, mode)
+            n = B * (C + Nc)
+            need = lib.nrms_news_encode_workspace_size(n, L, V, D, mode)
+            assert need > 0 and lib.nrms_news_encode(p, n, L, p, V, w, mode, p, p, need - 1, None) == short, (case, mode)
+        n = B * (C + Nc)
+        need = lib.nrms_news_encode_folded_workspace_size(n, L, D)
+        assert need > 0 and lib.nrms_news_encode_folded(p, n, L, p, 0, V, w, p, p, need - 1, None) == short, case
+        need = lib.nrms_user_encode_workspace_size(B, Nc, D)
+        assert need > 0 and lib.nrms_user_encode(p, B, Nc, Nc * D, D, w, p, p, need - 1, None) == short, case
+        for n_seq, length in ((n, L), (B, Nc)):
+            need = lib.nrms_additive_backward_workspace_size(n_seq, length, D, Q)
+            assert need > 0 and lib.nrms_additive_backward(p, n_seq, length, w, p, p, p, p, p, p, p, p, need - 1,
+                                                           None) == short, case
+        if L == 20:    # (the fused news tail's title length)
+            need = lib.nrms_news_attention_pool_workspace_size(n, L, D)
+            assert need > 0 and lib.nrms_news_attention_pool(p, 0, V, p, n, None, n, L, w, p, p, need - 1,
+                                                             None) == short, case
+        if Nc <= 64:   # (the fused UserEncoder's histories)
+            need = lib.nrms_user_attention_pool_workspace_size(B, Nc, D)
+            assert need > 0 and lib.nrms_user_attention_pool(p, 0, B, Nc, w, p, p, need - 1, None) == short, case
+            assert lib.nrms_user_attention_pool_padded(p, 0, B, Nc, p, w, p, p, need - 1, None) == short, case
