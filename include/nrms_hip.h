@@ -68,7 +68,9 @@ extern "C" {
  *    nrms_forward_prepared_workspace_size (and _folded_), nrms_forward_prepared
  *    and nrms_forward_prepared_timed.
  *    ABI 9, added later (additive, no bump): nrms_rank_impressions, and the
- *    host readers nrms_behaviors_scan_any / nrms_behaviors_parse_any. */
+ *    host readers nrms_behaviors_scan_any / nrms_behaviors_parse_any.
+ *    ABI 9, added later (additive, no bump): nrms_train_batch_gather and
+ *    nrms_xent_class0 (the fit loop's batch assembly and fused loss). */
 #define NRMS_ABI_VERSION 9
 
 typedef enum {
@@ -634,6 +636,33 @@ typedef struct {
 
 int32_t nrms_adam_step_multi(const nrms_adam_tensor_t* tensors, int32_t n, float lr, float beta1,
                              float beta2, float eps, int64_t step, hipStream_t stream);
+
+/* (ABI 9, added later) Batch assembly of the fit loop from a device-resident
+ * training set (BaseDataset.__getitem__ + default collate, src/dataset.py:
+ * 64-85). titles[n_title_rows, L]: the corpus titles (the caller appends an
+ * all-zero row for PADDED_NEWS); sample_rows[n_samples, C + N]: per training
+ * sample the title rows of its C candidates (positive first) and of its N
+ * history slots (left-padded with the zero row); sample_idx[B]: the samples of
+ * this batch. Writes cand_ids[B, C, L] and clicked_ids[B, N, L]:
+ *   out[b, j, l] = titles[sample_rows[sample_idx[b], j], l].
+ * A sample_idx[b] outside [0, n_samples) or a row outside [0, n_title_rows) is
+ * never dereferenced: that sample's titles, or that title, are written as
+ * zeros. One launch, nothing allocated, no host synchronisation. */
+int32_t nrms_train_batch_gather(const int64_t* titles, int64_t n_title_rows, int32_t L,
+                                const int32_t* sample_rows, int64_t n_samples, int32_t C, int32_t N,
+                                const int64_t* sample_idx, int64_t B,
+                                int64_t* cand_ids, int64_t* clicked_ids, hipStream_t stream);
+
+/* (ABI 9, added later) CrossEntropyLoss against class 0 and its gradient
+ * (src/train.py:126,205-206) in one launch, B >= 1 rows of any C >= 1:
+ *   loss_out[0]   = mean_b(logsumexp(z_b) - z_b0)       (DEVICE pointer)
+ *   dlogits[b, c] = (softmax(z_b)[c] - [c == 0]) / B
+ * with the row maximum subtracted first, as torch's log_softmax: a row holding
+ * +inf or NaN gives a NaN loss. The per-row losses are summed in a fixed order
+ * (fp64, no atomics): bitwise reproducible. One workgroup: meant for training
+ * batches (B in the hundreds), not for scoring a split. */
+int32_t nrms_xent_class0(const float* logits, int64_t B, int32_t C,
+                         float* dlogits, float* loss_out, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Host-side readers of the eval split (csrc/tsv_io.hip). HOST pointers, no

@@ -1088,6 +1088,25 @@ int32_t nrms_score_backward(const float* news, int64_t B, int32_t C, int64_t str
                                duser, stream);
 }
 
+int32_t nrms_train_batch_gather(const int64_t* titles, int64_t n_title_rows, int32_t L,
+                                const int32_t* sample_rows, int64_t n_samples, int32_t C, int32_t N,
+                                const int64_t* sample_idx, int64_t B, int64_t* cand_ids,
+                                int64_t* clicked_ids, hipStream_t stream) {
+  if (n_title_rows < 0 || n_samples < 0 || B < 0 || L <= 0 || C < 0 || N < 0) return NRMS_ERR_INVALID_ARG;
+  if (B == 0 || C + N == 0) return NRMS_OK;
+  if (!sample_idx || (C > 0 && !cand_ids) || (N > 0 && !clicked_ids)) return NRMS_ERR_INVALID_ARG;
+  if ((n_samples > 0 && !sample_rows) || (n_title_rows > 0 && !titles)) return NRMS_ERR_INVALID_ARG;
+  return launch_train_batch_gather(titles, n_title_rows, L, sample_rows, n_samples, C, N, sample_idx, B,
+                                   cand_ids, clicked_ids, stream);
+}
+
+int32_t nrms_xent_class0(const float* logits, int64_t B, int32_t C, float* dlogits, float* loss_out,
+                         hipStream_t stream) {
+  if (B <= 0 || C <= 0) return NRMS_ERR_INVALID_ARG;
+  if (!logits || !dlogits || !loss_out) return NRMS_ERR_INVALID_ARG;
+  return launch_xent_class0(logits, B, C, dlogits, loss_out, stream);
+}
+
 int32_t nrms_embedding_backward(const int64_t* ids, int64_t n_tok, const float* dx, int64_t V,
                                 int32_t D, int64_t padding_idx, float* dtable,
                                 hipStream_t stream) {

@@ -362,6 +362,13 @@ int32_t launch_adam_multi(const nrms_adam_tensor_t* ts, int n, float lr, float b
                           float eps, int64_t step, hipStream_t s);
 int32_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1,
                     float b2, float eps, int64_t step, hipStream_t s);
+// fit loop kernels (fit.hip); the contracts are nrms_train_batch_gather's and
+// nrms_xent_class0's (nrms_hip.h)
+int32_t launch_train_batch_gather(const int64_t* titles, int64_t n_title_rows, int L, const int32_t* sample_rows,
+                                  int64_t n_samples, int C, int N, const int64_t* sample_idx, int64_t B,
+                                  int64_t* cand_ids, int64_t* clicked_ids, hipStream_t s);
+int32_t launch_xent_class0(const float* logits, int64_t B, int C, float* dlogits, float* loss_out,
+                           hipStream_t s);
 
 // Device-side padding classification a deduplicating fused-news launch left
 // in its workspace: pad_title[t] = 1 for all-padding titles (20 zero ids), and

@@ -506,6 +506,50 @@ def write_behaviors(path, impressions):
             f.write(f"{im.impression_id}\t{im.user}\t{im.time}\t{hist}\t{imps}\n")
 
 
+def write_behaviors_parsed(path, users, histories, candidates, clicked):
+    """behaviors_parsed.tsv as src/data_preprocess.py:71-81 writes it: one row
+    per positive, `candidates` the positive followed by its K sampled
+    negatives, `clicked` the labels "1 0 0 ..."; an empty history is ' '."""
+    with open(path, "w") as f:
+        f.write("user\tclicked_news\tcandidate_news\tclicked\n")
+        for u, h, c, y in zip(users, histories, candidates, clicked):
+            f.write(f"{u}\t{' '.join(h) or ' '}\t{' '.join(c)}\t{' '.join(str(int(v)) for v in y)}\n")
+
+
+def synthetic_train_split(directory, seed=0, n_samples=1000, n_news=2000, V=70976, K=2, L=NUM_WORDS_TITLE,
+                          max_history=70, titles=None, positive=None):
+    """Write news_parsed.tsv + behaviors_parsed.tsv (the train split's two
+    files) under `directory`: titles as synthetic_split's, per sample a history
+    of U{0..max_history} clicked news (some empty, some past the 50-item
+    truncation) and 1 + K distinct candidates. `titles` [n_news, L] replaces
+    the drawn titles; `positive(cand_rows [n, 1+K], hist_rows list) -> [n]`
+    chooses which drawn candidate goes first (default: the first drawn).
+    Returns the NewsCorpus."""
+    rng = np.random.default_rng(seed)
+    os.makedirs(directory, exist_ok=True)
+    if titles is None:
+        lens = rng.integers(min(5, L), L + 1, n_news)
+        titles = rng.integers(1, V, (n_news, L))
+        titles[np.arange(L)[None, :] >= lens[:, None]] = 0
+    titles = np.asarray(titles, dtype=np.int64)
+    n_news = titles.shape[0]
+    ids = [f"N{i}" for i in range(n_news)]
+    hists = [rng.integers(0, n_news, int(rng.integers(0, max_history + 1))) for _ in range(n_samples)]
+    cands = np.stack([rng.choice(n_news, size=1 + K, replace=False) for _ in range(n_samples)])
+    if positive is not None:
+        first = np.asarray(positive(cands, hists), dtype=np.int64)
+        swap = cands[np.arange(n_samples), first].copy()
+        cands[np.arange(n_samples), first] = cands[:, 0]
+        cands[:, 0] = swap
+    write_news_parsed(os.path.join(directory, "news_parsed.tsv"), ids, titles)
+    write_behaviors_parsed(os.path.join(directory, "behaviors_parsed.tsv"),
+                           [f"U{k}" for k in range(n_samples)],
+                           [[f"N{x}" for x in h] for h in hists],
+                           [[f"N{x}" for x in c] for c in cands],
+                           [[1] + [0] * K] * n_samples)
+    return NewsCorpus(ids, titles)
+
+
 # ---------------------------------------------------------------- synthetic MIND-shaped split
 def synthetic_split(directory, seed=0, n_news=4000, n_users=600, n_impressions=2000, V=70976,
                     min_cands=2, max_cands=40, teacher=None, temperature=1.0):
