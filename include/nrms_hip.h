@@ -70,7 +70,9 @@ extern "C" {
  *    ABI 9, added later (additive, no bump): nrms_rank_impressions, and the
  *    host readers nrms_behaviors_scan_any / nrms_behaviors_parse_any.
  *    ABI 9, added later (additive, no bump): nrms_train_batch_gather and
- *    nrms_xent_class0 (the fit loop's batch assembly and fused loss). */
+ *    nrms_xent_class0 (the fit loop's batch assembly and fused loss).
+ *    ABI 9, added later (additive, no bump): nrms_train_batch_sample_gather
+ *    (batch assembly from raw impressions, negatives drawn in the launch). */
 #define NRMS_ABI_VERSION 9
 
 typedef enum {
@@ -652,6 +654,41 @@ int32_t nrms_train_batch_gather(const int64_t* titles, int64_t n_title_rows, int
                                 const int32_t* sample_rows, int64_t n_samples, int32_t C, int32_t N,
                                 const int64_t* sample_idx, int64_t B,
                                 int64_t* cand_ids, int64_t* clicked_ids, hipStream_t stream);
+
+/* (ABI 9, added later) nrms_train_batch_gather from a set that keeps the raw
+ * impressions of a behaviors.tsv: the K negatives of every sample are drawn in
+ * the launch, so each epoch sees new ones. A sample is one positive click:
+ * pos_row[n_samples] its title row, pos_imp[n_samples] its impression;
+ * neg_off[n_imps + 1] / neg_rows[n_neg]: CSR of the title rows of each
+ * impression's label-0 candidates; imp_hist[n_imps]: impression -> distinct
+ * history; hist_rows[n_hists, N]: the history's title rows (left-padded with
+ * the zero row). With s = sample_idx[b], i = pos_imp[s], n = neg_off[i + 1] -
+ * neg_off[i]:
+ *   cand_ids[b, 0, :]     = titles[pos_row[s]]
+ *   cand_ids[b, 1 + j, :] = titles[neg_rows[neg_off[i] + position_j]]
+ *   clicked_ids[b, k, :]  = titles[hist_rows[imp_hist[i], k]]
+ * The positions are a uniform ordered K-subset without replacement, a function
+ * of (seed, epoch, s) alone; all arithmetic uint64 and wrapping, mix() the
+ * splitmix64 finaliser (z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) *
+ * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31):
+ *   base = mix(mix(seed) + epoch)
+ *   for j in 0 .. K-1:  r = ((mix(base + 16 s + j) >> 32) * (n - j)) >> 32
+ *                       for p in ascending order of position_0..j-1: r += (r >= p)
+ *                       position_j = r
+ * No index is dereferenced unchecked: a sample_idx[b] outside [0, n_samples)
+ * zeroes the sample's titles; a pos_imp / imp_hist / row outside its table, a
+ * neg_off pair that decreases, is negative or runs past n_neg, and slots
+ * 1 + j with j >= n zero the titles that depend on them. K outside 0..15:
+ * NRMS_ERR_UNSUPPORTED, nothing launched. One launch, nothing allocated, no
+ * host synchronisation. */
+int32_t nrms_train_batch_sample_gather(const int64_t* titles, int64_t n_title_rows, int32_t L,
+                                       const int32_t* pos_row, const int32_t* pos_imp, int64_t n_samples,
+                                       const int64_t* neg_off, int64_t n_imps,
+                                       const int32_t* neg_rows, int64_t n_neg,
+                                       const int32_t* imp_hist, const int32_t* hist_rows, int64_t n_hists,
+                                       int32_t K, int32_t N, const int64_t* sample_idx, int64_t B,
+                                       uint64_t seed, int64_t epoch,
+                                       int64_t* cand_ids, int64_t* clicked_ids, hipStream_t stream);
 
 /* (ABI 9, added later) CrossEntropyLoss against class 0 and its gradient
  * (src/train.py:126,205-206) in one launch, B >= 1 rows of any C >= 1:

@@ -5,6 +5,6 @@ Maguire1999/NewsRecommendationSystem's ``model.NRMS``).
 """
 from .config import BaseConfig, NRMSConfig  # noqa: F401
 from .nrms import NRMS  # noqa: F401
-from .fit import TrainSet, fit  # noqa: F401
+from .fit import ImpressionSet, TrainSet, fit  # noqa: F401
 
-__all__ = ["NRMS", "NRMSConfig", "BaseConfig", "fit", "TrainSet"]
+__all__ = ["NRMS", "NRMSConfig", "BaseConfig", "fit", "TrainSet", "ImpressionSet"]

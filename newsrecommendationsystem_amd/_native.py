@@ -102,6 +102,8 @@ SIGNATURES = {
                                     ctypes.c_float, _i64, _p]),
     # fit loop (fit.py)
     "nrms_train_batch_gather": (_i32, [_p, _i64, _i32, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p]),
+    "nrms_train_batch_sample_gather": (_i32, [_p, _i64, _i32, _p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64,
+                                              _i32, _i32, _p, _i64, ctypes.c_uint64, _i64, _p, _p, _p]),
     "nrms_forward_workspace_size": (_sz, [_i64, _i32, _i32, _i32, _i64, _i32, _i32]),
     "nrms_forward": (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _i64, _EW, _EW, _i32, _p, _p,
                             _sz, _p]),

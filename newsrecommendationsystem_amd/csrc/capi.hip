@@ -1100,6 +1100,26 @@ int32_t nrms_train_batch_gather(const int64_t* titles, int64_t n_title_rows, int
                                    cand_ids, clicked_ids, stream);
 }
 
+int32_t nrms_train_batch_sample_gather(const int64_t* titles, int64_t n_title_rows, int32_t L,
+                                       const int32_t* pos_row, const int32_t* pos_imp, int64_t n_samples,
+                                       const int64_t* neg_off, int64_t n_imps, const int32_t* neg_rows,
+                                       int64_t n_neg, const int32_t* imp_hist, const int32_t* hist_rows,
+                                       int64_t n_hists, int32_t K, int32_t N, const int64_t* sample_idx, int64_t B,
+                                       uint64_t seed, int64_t epoch, int64_t* cand_ids, int64_t* clicked_ids,
+                                       hipStream_t stream) {
+  if (n_title_rows < 0 || n_samples < 0 || n_imps < 0 || n_neg < 0 || n_hists < 0 || B < 0 || L <= 0 || N < 0)
+    return NRMS_ERR_INVALID_ARG;
+  if (K < 0 || K > 15) return NRMS_ERR_UNSUPPORTED;
+  if (B == 0) return NRMS_OK;
+  if (!sample_idx || !cand_ids || (N > 0 && !clicked_ids)) return NRMS_ERR_INVALID_ARG;
+  if ((n_samples > 0 && (!pos_row || !pos_imp)) || (n_title_rows > 0 && !titles)) return NRMS_ERR_INVALID_ARG;
+  if (n_imps > 0 && (!neg_off || !imp_hist)) return NRMS_ERR_INVALID_ARG;
+  if ((n_neg > 0 && !neg_rows) || (n_hists > 0 && N > 0 && !hist_rows)) return NRMS_ERR_INVALID_ARG;
+  return launch_train_batch_sample_gather(titles, n_title_rows, L, pos_row, pos_imp, n_samples, neg_off, n_imps,
+                                          neg_rows, n_neg, imp_hist, hist_rows, n_hists, K, N, sample_idx, B, seed,
+                                          epoch, cand_ids, clicked_ids, stream);
+}
+
 int32_t nrms_xent_class0(const float* logits, int64_t B, int32_t C, float* dlogits, float* loss_out,
                          hipStream_t stream) {
   if (B <= 0 || C <= 0) return NRMS_ERR_INVALID_ARG;

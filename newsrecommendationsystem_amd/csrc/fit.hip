@@ -1,6 +1,7 @@
 // Kernels under the fit loop (newsrecommendationsystem_amd/fit.py): the batch
 // assembly of BaseDataset.__getitem__ + default collate (src/dataset.py:64-85)
-// from a device-resident training set, and CrossEntropyLoss against class 0
+// from a device-resident training set (drawn samples, or impressions whose
+// negatives are drawn in the same launch), and CrossEntropyLoss against class 0
 // with its gradient (src/train.py:205-206) in one launch.
 #include <math.h>
 
@@ -51,6 +52,102 @@ __global__ __launch_bounds__(kBatchGatherThreads) void train_batch_gather_kernel
   *out = v;
 }
 
+constexpr int kMaxSampledNegatives = 15;   // 16 hash slots per sample (16 s + j)
+
+// The splitmix64 finaliser (stream.mix on the host).
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
+  uint64_t z = x + 0x9E3779B97F4A7C15ULL;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+  return z ^ (z >> 31);
+}
+
+// Position, among the n negatives of its impression, of draw j of sample s: a
+// uniform ordered subset without replacement. Draw i takes r in [0, n - i)
+// from the high word of mix64(base + 16 s + i) and steps over the positions
+// chosen before it in ascending order, which makes r the r-th position still
+// free. The chosen positions are kept sorted in registers: every index into
+// `chosen` is a compile-time constant after unrolling (no scratch); the number
+// of positions r stepped over is also where r goes into the sorted list.
+// Draws 0 .. j are recomputed by every lane that needs draw j (at most 15
+// hashes; no LDS, no exchange between lanes).
+__device__ __forceinline__ uint64_t sampled_position(uint64_t base, uint64_t s, uint64_t n, int j) {
+  uint64_t chosen[kMaxSampledNegatives - 1];
+#pragma unroll
+  for (int k = 0; k < kMaxSampledNegatives - 1; ++k) chosen[k] = 0;
+  uint64_t r = 0;
+  for (int i = 0; i <= j; ++i) {
+    const uint64_t h = mix64(base + 16 * s + (uint64_t)i);
+    r = ((h >> 32) * (n - (uint64_t)i)) >> 32;
+    int q = 0;
+#pragma unroll
+    for (int k = 0; k < kMaxSampledNegatives - 1; ++k)
+      if (k < i && r >= chosen[k]) {
+        ++r;
+        ++q;
+      }
+    if (i == j) break;
+#pragma unroll
+    for (int k = kMaxSampledNegatives - 2; k >= 1; --k)
+      chosen[k] = k > q ? chosen[k - 1] : (k == q ? r : chosen[k]);
+    if (q == 0) chosen[0] = r;
+  }
+  return r;
+}
+
+// train_batch_gather_kernel's lane mapping over a set that keeps impressions,
+// not drawn samples (fit.ImpressionSet): candidate 0 of sample s is
+// pos_row[s], candidate 1 + j the negative at sampled_position(j) of the
+// sample's impression i = pos_imp[s] (neg_rows[neg_off[i] ..  neg_off[i + 1])),
+// the clicked titles are hist_rows[imp_hist[i]]. Every index read from a table
+// is checked against the next table's size before it is used; whatever depends
+// on a failed check is written as zeros.
+__global__ __launch_bounds__(kBatchGatherThreads) void train_batch_sample_gather_kernel(
+    const int64_t* __restrict__ titles, int64_t n_title_rows, int L, const int32_t* __restrict__ pos_row,
+    const int32_t* __restrict__ pos_imp, int64_t n_samples, const int64_t* __restrict__ neg_off, int64_t n_imps,
+    const int32_t* __restrict__ neg_rows, int64_t n_neg, const int32_t* __restrict__ imp_hist,
+    const int32_t* __restrict__ hist_rows, int64_t n_hists, int K, int N, const int64_t* __restrict__ sample_idx,
+    int64_t B, uint64_t base, int64_t* __restrict__ cand_ids, int64_t* __restrict__ clicked_ids) {
+  const int C = 1 + K;
+  const int64_t n_cand = B * C * L;
+  const int64_t total = n_cand + B * N * L;
+  const int64_t e = (int64_t)blockIdx.x * kBatchGatherThreads + threadIdx.x;
+  if (e >= total) return;
+  const bool is_cand = e < n_cand;
+  const int64_t r = is_cand ? e : e - n_cand;
+  const int64_t per = (int64_t)(is_cand ? C : N) * L;   // words of one sample in this output
+  const int64_t b = r / per;
+  const int64_t w = r - b * per;
+  const int j = (int)(w / L);
+  const int l = (int)(w - (int64_t)j * L);
+  int64_t* out = (is_cand ? cand_ids : clicked_ids) + r;
+  int64_t row = -1;
+  const int64_t s = sample_idx[b];
+  if ((uint64_t)s < (uint64_t)n_samples) {
+    if (is_cand && j == 0) {
+      row = pos_row[s];
+    } else {
+      const int64_t i = pos_imp[s];
+      if ((uint64_t)i < (uint64_t)n_imps) {
+        if (is_cand) {
+          const int64_t o0 = neg_off[i], o1 = neg_off[i + 1];
+          if (o0 >= 0 && o0 <= o1 && o1 <= n_neg && (int64_t)(j - 1) < o1 - o0) {
+            const uint64_t n = (uint64_t)(o1 - o0);
+            const uint64_t p = sampled_position(base, (uint64_t)s, n, j - 1);
+            if (p < n) row = neg_rows[o0 + (int64_t)p];
+          }
+        } else {
+          const int64_t h = imp_hist[i];
+          if ((uint64_t)h < (uint64_t)n_hists) row = hist_rows[h * N + j];
+        }
+      }
+    }
+  }
+  int64_t v = 0;
+  if ((uint64_t)row < (uint64_t)n_title_rows) v = titles[row * L + l];
+  *out = v;
+}
+
 constexpr int kXentWaves = 16;
 
 // One workgroup; wave w takes rows w, w + 16, ... in turn, lanes stride over
@@ -98,6 +195,24 @@ int32_t launch_train_batch_gather(const int64_t* titles, int64_t n_title_rows, i
   if (blocks > INT32_MAX) return NRMS_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(train_batch_gather_kernel, dim3((unsigned)blocks), dim3(kBatchGatherThreads), 0, s, titles,
                      n_title_rows, L, sample_rows, n_samples, C, N, sample_idx, B, cand_ids, clicked_ids);
+  return launch_status();
+}
+
+int32_t launch_train_batch_sample_gather(const int64_t* titles, int64_t n_title_rows, int L, const int32_t* pos_row,
+                                         const int32_t* pos_imp, int64_t n_samples, const int64_t* neg_off,
+                                         int64_t n_imps, const int32_t* neg_rows, int64_t n_neg,
+                                         const int32_t* imp_hist, const int32_t* hist_rows, int64_t n_hists, int K,
+                                         int N, const int64_t* sample_idx, int64_t B, uint64_t seed, int64_t epoch,
+                                         int64_t* cand_ids, int64_t* clicked_ids, hipStream_t s) {
+  if (K < 0 || K > kMaxSampledNegatives) return NRMS_ERR_UNSUPPORTED;
+  const int64_t total = B * ((int64_t)1 + K + N) * L;
+  if (total == 0) return NRMS_OK;
+  const int64_t blocks = (total + kBatchGatherThreads - 1) / kBatchGatherThreads;
+  if (blocks > INT32_MAX) return NRMS_ERR_UNSUPPORTED;
+  const uint64_t base = mix64(mix64(seed) + (uint64_t)epoch);
+  hipLaunchKernelGGL(train_batch_sample_gather_kernel, dim3((unsigned)blocks), dim3(kBatchGatherThreads), 0, s,
+                     titles, n_title_rows, L, pos_row, pos_imp, n_samples, neg_off, n_imps, neg_rows, n_neg,
+                     imp_hist, hist_rows, n_hists, K, N, sample_idx, B, base, cand_ids, clicked_ids);
   return launch_status();
 }
 

@@ -369,6 +369,13 @@ int32_t launch_train_batch_gather(const int64_t* titles, int64_t n_title_rows, i
                                   int64_t* cand_ids, int64_t* clicked_ids, hipStream_t s);
 int32_t launch_xent_class0(const float* logits, int64_t B, int C, float* dlogits, float* loss_out,
                            hipStream_t s);
+// nrms_train_batch_sample_gather's contract (nrms_hip.h); K in 0..15
+int32_t launch_train_batch_sample_gather(const int64_t* titles, int64_t n_title_rows, int L, const int32_t* pos_row,
+                                         const int32_t* pos_imp, int64_t n_samples, const int64_t* neg_off,
+                                         int64_t n_imps, const int32_t* neg_rows, int64_t n_neg,
+                                         const int32_t* imp_hist, const int32_t* hist_rows, int64_t n_hists, int K,
+                                         int N, const int64_t* sample_idx, int64_t B, uint64_t seed, int64_t epoch,
+                                         int64_t* cand_ids, int64_t* clicked_ids, hipStream_t s);
 
 // Device-side padding classification a deduplicating fused-news launch left
 // in its workspace: pad_title[t] = 1 for all-padding titles (20 zero ids), and

@@ -13,7 +13,11 @@ the GPU would wait on, so here
   * nrms_xent_class0 computes CrossEntropyLoss against class 0 and its
     gradient in one launch and leaves the loss in a device log, read back only
     when a log line or a validation needs it;
-  * the sample order of an epoch is uploaded once per epoch.
+  * the sample order of an epoch is uploaded once per epoch;
+  * ImpressionSet keeps a raw behaviors.tsv per impression instead, and
+    nrms_train_batch_sample_gather draws each sample's K negatives in the
+    gather launch, as a counter-based hash of (seed, epoch, sample): new
+    negatives every epoch, no per-epoch table, nothing uploaded.
 
 What is kept from the reference: shuffled drop_last batches, validation every
 num_batches_validate steps, EarlyStopping(patience 5) on -AUC, ckpt-{step}.pth
@@ -126,6 +130,270 @@ class TrainSet:
         return out
 
 
+MAX_SAMPLED_NEGATIVES = 15          # the sampler keeps 16 hash slots per sample (16 s + j)
+_U64 = (1 << 64) - 1
+
+
+def mix64(x):
+    """The splitmix64 finaliser (stream.mix) on a Python int, mod 2^64."""
+    z = (int(x) + 0x9E3779B97F4A7C15) & _U64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _U64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _U64
+    return z ^ (z >> 31)
+
+
+def sampler_base(seed, epoch):
+    """mix(mix(uint64(seed)) + uint64(epoch)): the key of one epoch's draws."""
+    return mix64((mix64(int(seed) & _U64) + (int(epoch) & _U64)) & _U64)
+
+
+def _mix64_np(x):
+    z = x + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def draw_positions(seed, epoch, s, n, k):
+    """The sampler of nrms_train_batch_sample_gather on the host (numpy, all
+    arithmetic uint64 and wrapping): int64 [B, k], row b the positions, among
+    n[b] negatives, of the k draws of sample s[b] in epoch `epoch`: a uniform
+    ordered k-subset without replacement, a function of (seed, epoch, s) alone.
+
+        base = mix(mix(seed) + epoch)
+        r    = ((mix(base + 16 s + j) >> 32) * (n - j)) >> 32     in [0, n - j)
+        for p in ascending order of the positions chosen before: r += (r >= p)
+
+    -1 where the kernel writes zeros: draws j >= n (and a position that n >=
+    2^32 would let wrap past n)."""
+    s = np.asarray(s, dtype=np.int64).reshape(-1)
+    n = np.broadcast_to(np.asarray(n, dtype=np.int64), s.shape)
+    B, k = s.size, int(k)
+    if not 0 <= k <= MAX_SAMPLED_NEGATIVES:
+        raise ValueError(f"K = {k} outside 0..{MAX_SAMPLED_NEGATIVES}")
+    out = np.full((B, k), -1, dtype=np.int64)
+    su, nu = s.astype(np.uint64), n.astype(np.uint64)
+    key = np.uint64(sampler_base(seed, epoch)) + np.uint64(16) * su
+    chosen = np.zeros((B, k), dtype=np.uint64)            # columns [0, j): ascending
+    for j in range(k):
+        h = _mix64_np(key + np.uint64(j))
+        r = ((h >> np.uint64(32)) * (nu - np.uint64(j))) >> np.uint64(32)
+        for c in range(j):
+            r = r + (r >= chosen[:, c]).astype(np.uint64)
+        ok = (n > j) & (r < nu)
+        out[ok, j] = r[ok].astype(np.int64)
+        chosen[:, j] = r
+        chosen[:, :j + 1].sort(axis=1)
+    return out
+
+
+class ImpressionSet:
+    """A labelled raw behaviors.tsv as a training set whose negatives are drawn
+    anew for every (seed, epoch): what TrainSet holds per sample, kept per
+    impression.
+
+    A sample is one positive click; samples are ordered by impression, then by
+    candidate position.
+      titles    int64 [n_news + 1, L]  corpus titles + the all-zero padding title
+      pos_row   int32 [S]              corpus row of sample s's clicked article
+      pos_imp   int32 [S]              its impression
+      neg_off   int64 [I + 1], neg_rows int32 [T]
+                                       CSR of each impression's label-0
+                                       candidates, in file order
+      imp_hist  int32 [I]              impression -> distinct history string
+      hist_rows int32 [H, N]           first N history items, left-padded with
+                                       the padding row (as TrainSet)
+    (each also as *_host numpy copies). The positives of an impression with
+    fewer than K negatives are not samples (the reference's balancing drops
+    incomplete groups, src/data_preprocess.py:55-68); n_dropped counts them.
+    ValueError: K outside 0..15, an unknown news id, a label other than 0/1, no
+    sample left.
+
+    On purpose not the reference: every positive draws its own K of ALL the
+    impression's negatives (draw_positions), so two positives of one impression
+    may share a negative, and no positive is dropped because the negatives ran
+    out; the reference deals one shuffled negative list out across the
+    positives, once, offline."""
+
+    def __init__(self, behaviors_path, corpus, k=None, num_clicked=NUM_CLICKED, device="cpu"):
+        from .config import NRMSConfig
+        from .data import (BehaviorsTable, _index_rows, candidate_rows_numeric, load_behaviors, numeric_news_index,
+                           parse_impression_cells)
+        from .evaluate import history_rows_of, lookup_rows, table_history_rows, users_by_history
+        K = int(NRMSConfig.negative_sampling_ratio if k is None else k)
+        if not 0 <= K <= MAX_SAMPLED_NEGATIVES:
+            raise ValueError(f"K = {K} outside 0..{MAX_SAMPLED_NEGATIVES}")
+        n_news, L = corpus.titles.shape
+        pad = n_news
+        if n_news + 1 > np.iinfo(np.int32).max:
+            raise ValueError("more news than int32 rows address")
+        imps = load_behaviors(behaviors_path)
+        nindex = numeric_news_index(corpus)
+        try:
+            if isinstance(imps, BehaviorsTable) and nindex is not None:
+                cand, labels, counts = _index_rows(nindex, imps.cand_num), imps.labels, imps.cand_count
+                imp_hist = imps.hist_user
+                hist_rows = table_history_rows(imps, nindex, num_clicked, pad)
+            else:
+                imps = list(imps)
+                imp_hist, hists = users_by_history(imps)
+                fast = candidate_rows_numeric(imps, nindex)
+                if fast is not None:
+                    cand, labels, counts = fast
+                else:
+                    names, labels, counts = parse_impression_cells(imps)
+                    cand = lookup_rows(corpus, names)
+                hist_rows = history_rows_of(corpus, hists, nindex, num_clicked)
+        except KeyError as e:
+            raise ValueError(f"{behaviors_path}: unknown news id {e}") from None
+        labels = np.asarray(labels, dtype=np.int64)
+        counts = np.asarray(counts, dtype=np.int64)
+        if ((labels != 0) & (labels != 1)).any():
+            bad = int(labels[(labels != 0) & (labels != 1)][0])
+            raise ValueError(f"{behaviors_path}: label {bad}, a training split needs 0/1 labels")
+        I = counts.size
+        imp_of = np.repeat(np.arange(I, dtype=np.int64), counts)
+        neg = labels == 0
+        n_neg = np.bincount(imp_of[neg], minlength=I).astype(np.int64)
+        keep = ~neg & (n_neg[imp_of] >= K)
+        self.n_dropped = int((~neg).sum() - keep.sum())
+        if not keep.any():
+            raise ValueError(f"{behaviors_path}: no samples (no positive in an impression with >= {K} negatives)")
+        if cand.size > np.iinfo(np.int32).max or I > np.iinfo(np.int32).max:
+            raise ValueError("more candidates or impressions than int32 addresses")
+        self.K, self.C, self.N, self.L = K, 1 + K, int(num_clicked), int(L)
+        self.pos_row_host = cand[keep].astype(np.int32)
+        self.pos_imp_host = imp_of[keep].astype(np.int32)
+        self.neg_off_host = np.concatenate([[0], np.cumsum(n_neg)]).astype(np.int64)
+        self.neg_rows_host = cand[neg].astype(np.int32)
+        self.imp_hist_host = np.asarray(imp_hist, dtype=np.int32)
+        self.hist_rows_host = np.ascontiguousarray(hist_rows, dtype=np.int32).reshape(-1, self.N)
+        self.titles_host = np.concatenate([corpus.titles, np.zeros((1, L), np.int64)])
+        self.max_id = int(self.titles_host.max()) if self.titles_host.size else 0
+        self.min_id = int(self.titles_host.min()) if self.titles_host.size else 0
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        for name in ("titles", "pos_row", "pos_imp", "neg_off", "neg_rows", "imp_hist", "hist_rows"):
+            setattr(self, name, torch.from_numpy(getattr(self, name + "_host")).to(self.device))
+        self._ids, self._imps = corpus.ids, imps           # names, for export_epoch
+        self._out = {}
+        self._seed = self._epoch = None
+
+    def __len__(self):
+        return self.pos_row_host.shape[0]
+
+    @property
+    def device_bytes(self):
+        return sum(getattr(self, n).numel() * getattr(self, n).element_size()
+                   for n in ("titles", "pos_row", "pos_imp", "neg_off", "neg_rows", "imp_hist", "hist_rows"))
+
+    def begin_epoch(self, seed, epoch):
+        """The (seed, epoch) that batch / host_batch draw with when a call
+        names none: fit() calls this when an epoch begins."""
+        self._seed, self._epoch = int(seed), int(epoch)
+
+    def _key(self, seed, epoch):
+        seed = self._seed if seed is None else seed
+        epoch = self._epoch if epoch is None else epoch
+        if seed is None or epoch is None:
+            raise ValueError("ImpressionSet draws per (seed, epoch): pass them or call begin_epoch first")
+        return int(seed), int(epoch)
+
+    def _sample_tables(self, sample_idx):
+        """Per sample of the batch, with the kernel's checks: (sample valid,
+        clamped sample, impression valid, clamped impression, negatives'
+        offset, negatives' count (0 where neg_off is unusable))."""
+        idx = np.asarray(torch.as_tensor(sample_idx).cpu(), dtype=np.int64).reshape(-1)
+        ok_s = (idx >= 0) & (idx < len(self))
+        s = np.where(ok_s, idx, 0)
+        i = self.pos_imp_host[s].astype(np.int64)
+        ok_i = ok_s & (i >= 0) & (i < self.imp_hist_host.shape[0])
+        i = np.where(ok_i, i, 0)
+        o0, o1 = self.neg_off_host[i], self.neg_off_host[i + 1]
+        ok_o = ok_i & (o0 >= 0) & (o0 <= o1) & (o1 <= self.neg_rows_host.shape[0])
+        return idx, ok_s, s, ok_i, i, np.where(ok_o, o0, 0), np.where(ok_o, o1 - o0, 0)
+
+    def draws(self, seed, epoch, sample_idx):
+        """int64 [B, K]: the positions, within the negative list of each
+        sample's impression, that (seed, epoch) draws (draw_positions); -1
+        where the batch gets zeros instead."""
+        idx, _, _, _, _, _, n = self._sample_tables(sample_idx)
+        return draw_positions(seed, epoch, idx, n, self.K)
+
+    def _rows(self, sample_idx, seed, epoch):
+        """int64 [B, C + N] title rows of the batch, -1 where the kernel
+        writes zeros."""
+        idx, ok_s, s, ok_i, i, o0, n = self._sample_tables(sample_idx)
+        rows = np.full((idx.size, self.C + self.N), -1, dtype=np.int64)
+        rows[:, 0] = np.where(ok_s, self.pos_row_host[s], -1)
+        if self.K:
+            pos = draw_positions(seed, epoch, idx, n, self.K)
+            got = pos >= 0
+            at = np.where(got, o0[:, None] + pos, 0)
+            rows[:, 1:self.C] = np.where(got, self.neg_rows_host[at] if self.neg_rows_host.size else -1, -1)
+        h = self.imp_hist_host[i].astype(np.int64)
+        ok_h = ok_i & (h >= 0) & (h < self.hist_rows_host.shape[0])
+        if self.N and self.hist_rows_host.shape[0]:
+            rows[:, self.C:] = np.where(ok_h[:, None], self.hist_rows_host[np.where(ok_h, h, 0)], -1)
+        rows[(rows < 0) | (rows >= self.titles_host.shape[0])] = -1
+        return rows
+
+    def host_batch(self, sample_idx, seed=None, epoch=None):
+        """(cand [B, C, L], clicked [B, N, L]) int64 CPU tensors: the numpy
+        mirror of nrms_train_batch_sample_gather, its zeros included."""
+        seed, epoch = self._key(seed, epoch)
+        rows = self._rows(sample_idx, seed, epoch)
+        g = self.titles_host[np.where(rows >= 0, rows, 0)]
+        g[rows < 0] = 0
+        return (torch.from_numpy(np.ascontiguousarray(g[:, :self.C])),
+                torch.from_numpy(np.ascontiguousarray(g[:, self.C:])))
+
+    def batch(self, sample_idx, seed=None, epoch=None):
+        """(cand [B, C, L], clicked [B, N, L]) int64 on the set's device. On a
+        GPU: one nrms_train_batch_sample_gather launch (draw + gather) into two
+        buffers this set owns (one pair per batch size; the next call with the
+        same B overwrites them), nothing allocated, no host synchronisation
+        when sample_idx is already an int64 tensor on the device."""
+        seed, epoch = self._key(seed, epoch)
+        if self.device.type != "cuda":
+            return self.host_batch(sample_idx, seed, epoch)
+        import ctypes
+        idx = torch.as_tensor(sample_idx).to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+        B = idx.numel()
+        out = self._out.get(B)
+        if out is None:
+            out = self._out[B] = (torch.empty(B, self.C, self.L, dtype=torch.int64, device=self.device),
+                                  torch.empty(B, self.N, self.L, dtype=torch.int64, device=self.device))
+        N.call("nrms_train_batch_sample_gather", N.ptr(self.titles), self.titles.shape[0], self.L,
+               N.ptr(self.pos_row), N.ptr(self.pos_imp), self.pos_row.shape[0], N.ptr(self.neg_off),
+               self.imp_hist.shape[0], N.ptr(self.neg_rows), self.neg_rows.shape[0], N.ptr(self.imp_hist),
+               N.ptr(self.hist_rows), self.hist_rows.shape[0], self.K, self.N, N.ptr(idx), B,
+               ctypes.c_uint64(seed & _U64), epoch, N.ptr(out[0]), N.ptr(out[1]), N.stream_handle(self.device))
+        return out
+
+    def materialize(self, seed, epoch):
+        """int32 [S, C + N]: the row table a TrainSet would hold for this
+        epoch's draw (the padding row where the kernel writes zeros)."""
+        rows = self._rows(np.arange(len(self)), seed, epoch)
+        rows[rows < 0] = self.titles_host.shape[0] - 1
+        return rows.astype(np.int32)
+
+    def export_epoch(self, path, seed, epoch):
+        """Write the epoch's samples as a behaviors_parsed.tsv
+        (data.write_behaviors_parsed): what TrainSet and the reference's
+        BaseDataset read."""
+        from .data import BehaviorsTable, write_behaviors_parsed
+        rows = self.materialize(seed, epoch)
+        pad = self.titles_host.shape[0] - 1
+        ids = self._ids
+        users = self._imps.users() if isinstance(self._imps, BehaviorsTable) else [im.user for im in self._imps]
+        write_behaviors_parsed(path, [users[i] for i in self.pos_imp_host.tolist()],
+                               [[ids[r] for r in h if r != pad] for h in rows[:, self.C:].tolist()],
+                               [[ids[r] for r in c] for c in rows[:, :self.C].tolist()],
+                               [[1] + [0] * self.K] * len(self))
+
+
 def xent_class0(logits, dlogits=None, loss_out=None):
     """nrms_xent_class0 on a contiguous fp32 CUDA [B, C]: (loss [1] device
     tensor, dlogits [B, C]). loss_out: a one-element view to write the loss to
@@ -222,7 +490,9 @@ class _DirValidator:
 
 def fit(model, train_set, val=None, *, checkpoint_dir=None, seed=0, steps=None, batch_size=None,
         validate=None, log=print, host_batches=False):
-    """The reference's train() on `train_set` (module docstring). `validate`:
+    """The reference's train() on `train_set` (module docstring): a TrainSet
+    (the file's static negatives), or an ImpressionSet, whose negatives epoch
+    e draws with the loop's (seed, e) -- told through begin_epoch. `validate`:
     callable model -> AUC; else `val`: a directory with news_parsed.tsv and
     behaviors.tsv; neither: no validation, no checkpoints. `steps`: how many
     steps this call runs (default: up to num_epochs * S // batch_size in
@@ -273,6 +543,7 @@ def fit(model, train_set, val=None, *, checkpoint_dir=None, seed=0, steps=None, 
             pending.clear()
 
     epoch, order = None, None
+    begin_epoch = getattr(train_set, "begin_epoch", None)   # an ImpressionSet draws per (seed, epoch)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
@@ -281,6 +552,8 @@ def fit(model, train_set, val=None, *, checkpoint_dir=None, seed=0, steps=None, 
         e, a, b = batch_of_step(t, S, B)
         if e != epoch:
             epoch, order = e, epoch_order(seed, e, S)
+            if begin_epoch is not None:
+                begin_epoch(seed, e)
             if dev.type == "cuda" and not host_batches:
                 order = order.to(dev)
         if host_batches:

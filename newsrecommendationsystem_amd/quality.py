@@ -283,3 +283,52 @@ def run_scaled(steps=320, every=10, world=2, B=128, C=3, V=70976, n_news=20000, 
                 "reference_train_steps_per_s": round(world * n / t_ref, 1)})
             torch.cuda.empty_cache()
     return res
+
+
+# ---------------------------------------------------------------- static vs resampled negatives
+def resample_vs_static(epochs=6, B=64, V=5000, n_news=3000, n_users=800, n_impressions=1500, k=2, lr=5e-4,
+                       dropout=0.2, seed=0, temperature=0.5):
+    """One planted-teacher run of fit() per route, same student, seeds and
+    epochs: on the TrainSet of the ImpressionSet's exported epoch 0 (the static
+    negatives a behaviors_parsed.tsv would hold) and on the ImpressionSet (new
+    negatives every epoch). Train and validation splits are two
+    synthetic_split draws labelled by the teacher, impressions of 10-40
+    candidates. lr: setup()'s 2e-3 is meant for a few hundred steps; over the
+    ~2,000 steps of six epochs here both routes reached a NaN loss in epoch 5
+    with it, so the default is lower. temperature: run_scaled's 0.5. Returns
+    the report text: validation AUC after each epoch."""
+    import os
+
+    from .fit import ImpressionSet, TrainSet, fit
+    dev = torch.device("cuda", 0)
+    cfg = make_config(V, lr, dropout)
+    teacher = model_from_seed(cfg, 1000 + seed).to(dev).eval()
+    with tempfile.TemporaryDirectory() as d:
+        tr, va = os.path.join(d, "train"), os.path.join(d, "val")
+        for path, s in ((tr, seed + 1), (va, seed)):
+            Dt.synthetic_split(path, seed=s, n_news=n_news, n_users=n_users, n_impressions=n_impressions, V=V,
+                               min_cands=10, max_cands=40, teacher=teacher_logits_fn(teacher), temperature=temperature)
+        corpus = Dt.read_news_parsed(os.path.join(tr, "news_parsed.tsv"))
+        iset = ImpressionSet(os.path.join(tr, "behaviors.tsv"), corpus, k=k, device=dev)
+        iset.export_epoch(os.path.join(tr, "behaviors_parsed.tsv"), seed, 0)
+        static = TrainSet(os.path.join(tr, "behaviors_parsed.tsv"), corpus, device=dev)
+        per = len(iset) // B
+        student = model_from_seed(cfg, 2000 + seed)
+        student.config = type("ResampleCfg", (cfg,), dict(num_batches_validate=per, num_batches_show_loss=0))
+        runs = {}
+        for name, s in (("static (epoch-0 file)", static), ("resampled", iset)):
+            m = copy.deepcopy(student).to(dev)
+            r = fit(m, s, va, seed=seed, steps=epochs * per, batch_size=B, log=lambda *_: None)
+            runs[name] = r
+    lines = [f"planted teacher, static vs resampled negatives: {len(iset)} samples of {iset.imp_hist.shape[0]} "
+             f"train impressions (10-40 candidates, {iset.neg_rows.shape[0]} negatives, {iset.n_dropped} positives "
+             f"dropped), 1+K = {1 + k}, B = {B}, {per} steps per epoch, {epochs} epochs, V = {V}, {n_news} news, "
+             f"lr {lr}, dropout {dropout}, seed {seed}; validation: {n_impressions} impressions of another draw, "
+             f"labels ~ Bernoulli(sigmoid(teacher logit / {temperature})); one run per route, "
+             f"{torch.cuda.get_device_name(dev)}",
+             "validation AUC after each epoch:"]
+    for name, r in runs.items():
+        lines.append(f"  {name:22s} " + "  ".join(f"{a:.4f}" for _, a in r.aucs) +
+                     ("  (early stop)" if r.early_stopped else "") +
+                     f"   final loss {float(r.losses[-1]):.4f}")
+    return "\n".join(lines) + "\n"
