@@ -104,6 +104,7 @@ SIGNATURES = {
     "nrms_train_batch_gather": (_i32, [_p, _i64, _i32, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p]),
     "nrms_train_batch_sample_gather": (_i32, [_p, _i64, _i32, _p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64,
                                               _i32, _i32, _p, _i64, ctypes.c_uint64, _i64, _p, _p, _p]),
+    "nrms_xent_class0": (_i32, [_p, _i64, _i32, _p, _p, _p]),
     "nrms_forward_workspace_size": (_sz, [_i64, _i32, _i32, _i32, _i64, _i32, _i32]),
     "nrms_forward": (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _i64, _EW, _EW, _i32, _p, _p,
                             _sz, _p]),
@@ -124,12 +125,6 @@ SIGNATURES = {
     "nrms_behaviors_scan_any": (_i32, [_p, _i64, _p]),
     "nrms_behaviors_parse_any": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "nrms_news_parse": (_i32, [_p, _i64, _i32, _p, _p, _p, _p, _i64]),
-}
-# Entry points whose names carry a digit, typed at load like the table above.
-# Kept apart because tests/test_host_cpu.py compares SIGNATURES with the names
-# its letters-only pattern finds in the header.
-SIGNATURES_DIGIT = {
-    "nrms_xent_class0": (_i32, [_p, _i64, _i32, _p, _p, _p]),   # fit loop (fit.py)
 }
 NRMS_RANK_ORDER, NRMS_RANK_SHARED = 0, 1
 NRMS_RANK_LDS_CANDIDATES = 2048
@@ -152,7 +147,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -m newsrecommendationsystem_amd.build` "
             "(there is no CPU or eager fallback for the NRMS HIP path)")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **SIGNATURES_DIGIT}.items():
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -33,6 +33,20 @@ def load(path, map_location="cpu"):
         return torch.load(path, map_location=map_location, weights_only=True)
 
 
+def load_model(path, device="cpu"):
+    """The checkpoint's model on `device`, in eval mode: an NRMS whose
+    num_words and word_embedding_dim are the saved embedding table's shape
+    (the other hyper-parameters are NRMSConfig's)."""
+    from .config import NRMSConfig
+    from .nrms import NRMS
+    state = load(path)["model_state_dict"]
+    V, D = state["news_encoder.word_embedding.weight"].shape
+    cfg = type("CheckpointCfg", (NRMSConfig,), dict(num_words=int(V), word_embedding_dim=int(D)))
+    model = NRMS(cfg)
+    model.load_state_dict(state)
+    return model.to(torch.device(device)).eval()
+
+
 def latest_checkpoint(directory):
     """Path of the ckpt-{step}.pth with the largest step, or None
     (src/train.py:54-64)."""

@@ -24,116 +24,31 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .data import (PADDED_NEWS, BehaviorsTable, _index_rows, candidate_rows_numeric, history_ids,
-                   history_rows_numeric, load_behaviors, numeric_news_index, parse_impression_cells,
-                   read_news_parsed)
+from .data import load_behaviors, read_news_parsed
+from .splits import index_split
 
 
 class EvalPlan:
-    """Host-side index arrays for one split (built once, reused per model).
-
-    The impressions cells of the split are parsed in one pass
-    (data.parse_impression_cells) and every candidate / history id is mapped to
-    its corpus row in one flat pass each (the reference looks candidates up
-    inside its per-impression loop, src/evaluate.py:251-255); an unknown id
-    raises KeyError as news2vector[...] does."""
+    """Host-side index arrays for one split (built once, reused per model):
+    splits.index_split's arrays of the impressions max_count leaves, and the
+    user row of every (impression, candidate) pair. An unknown id raises
+    KeyError as news2vector[...] does."""
 
     def __init__(self, corpus, impressions, max_count=sys.maxsize, num_clicked=50):
         # the reference breaks when count == max_count before scoring it
         # (src/evaluate.py:245-249): impressions 1..max_count-1 are scored
         n = len(impressions) if max_count > len(impressions) else max(0, max_count - 1)
+        split = index_split(corpus, impressions if n == len(impressions) else impressions[:n], num_clicked)
         self.corpus = corpus
         self.num_clicked = num_clicked
-        pad = len(corpus)
-        if isinstance(impressions, BehaviorsTable):
-            tab = impressions if n == len(impressions) else impressions[:n]
-            nindex = numeric_news_index(corpus)
-            if nindex is not None:
-                self._from_table(tab, nindex, num_clicked, pad)
-                return
-            impressions = list(tab)   # (ids not in the numeric form: the per-name path)
-        self.impressions = impressions[:n]
-        imp_user, hists = users_by_history(self.impressions)
-        # MIND-form cells ("N<digits>-<label>"): one numeric parse and an array
-        # index (data.candidate_rows_numeric); any other form: the per-name path
-        nindex = numeric_news_index(corpus)
-        fast = candidate_rows_numeric(self.impressions, nindex)
-        if fast is not None:
-            self.cand, self.labels, counts = fast
-        else:
-            cand_names, self.labels, counts = parse_impression_cells(self.impressions)
-            self.cand = lookup_rows(corpus, cand_names)
-        self.pair_user = np.repeat(imp_user, counts)
-        self.offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        self.hist_rows = history_rows_of(corpus, hists, nindex, num_clicked)
-
-    def _from_table(self, tab, nindex, num_clicked, pad):
-        """The plan from a natively parsed split (data.BehaviorsTable): the
-        same arrays as the Impression path's numeric fast path."""
-        self.impressions = tab
-        self.cand = _index_rows(nindex, tab.cand_num)
-        self.labels = tab.labels
-        counts = tab.cand_count
-        self.pair_user = np.repeat(tab.hist_user, counts)
-        self.offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        self.hist_rows = table_history_rows(tab, nindex, num_clicked, pad)
+        self.impressions = split.impressions
+        self.cand, self.labels = split.cand, split.labels
+        self.offsets, self.hist_rows = split.offsets, split.hist_rows
+        self.pair_user = np.repeat(split.imp_user, split.counts)
 
     @property
     def n_impressions(self):
         return len(self.offsets) - 1
-
-
-def users_by_history(impressions):
-    """(user index int64 per impression, the distinct history strings): users
-    are keyed by history string, numbered in first-seen order."""
-    hist_of = {}
-    hists = []
-    imp_user = np.empty(len(impressions), dtype=np.int64)
-    for k, im in enumerate(impressions):
-        u = hist_of.get(im.clicked_news)
-        if u is None:
-            u = hist_of[im.clicked_news] = len(hists)
-            hists.append(im.clicked_news)
-        imp_user[k] = u
-    return imp_user, hists
-
-
-def lookup_rows(corpus, names):
-    """corpus rows of news ids by name: id -> first row (news2vector[...],
-    evaluate.py:255); an unknown id raises KeyError."""
-    return np.fromiter(map(corpus.index.__getitem__, names), dtype=np.int64, count=len(names))
-
-
-def history_rows_of(corpus, hists, nindex, num_clicked):
-    """[len(hists), num_clicked] corpus rows of each history string's first
-    num_clicked ids, left-padded with len(corpus): the numeric pass when the
-    ids allow, the per-name lookup otherwise."""
-    pad = len(corpus)
-    hrows = history_rows_numeric(hists, nindex, num_clicked, pad)
-    if hrows is None:
-        hist_names = [x for h in hists for x in history_ids(h, num_clicked)]
-        real = np.array([x != PADDED_NEWS for x in hist_names], dtype=bool)
-        rows = np.full(len(hist_names), pad, dtype=np.int64)
-        if real.any():
-            rows[real] = lookup_rows(corpus, [x for x, r in zip(hist_names, real) if r])
-        hrows = rows.reshape(len(hists), num_clicked)
-    return hrows
-
-
-def table_history_rows(tab, nindex, num_clicked, pad):
-    """The same rows from a BehaviorsTable: each distinct history's first
-    line, its first num_clicked ids, left-padded."""
-    imp_user = tab.hist_user
-    _, first = np.unique(imp_user, return_index=True) if len(tab) else (None, np.zeros(0, np.int64))
-    U = first.size
-    hc, ho = tab.hist_count[first], tab.hist_off[first]
-    m = np.minimum(hc, num_clicked)
-    rows = np.full((U, num_clicked), pad, dtype=np.int64)
-    if int(m.sum()):
-        u = np.repeat(np.arange(U), m)
-        k = np.arange(int(m.sum())) - np.repeat(np.cumsum(m) - m, m)
-        rows[u, num_clicked - np.repeat(m, m) + k] = _index_rows(nindex, tab.hist_num[np.repeat(ho, m) + k])
-    return rows
 
 
 @torch.no_grad()

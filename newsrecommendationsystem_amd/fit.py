@@ -39,10 +39,53 @@ import torch
 from . import _native as N
 from . import checkpoint as CK
 from . import train as TR
-from .data import NUM_CLICKED
+from .data import NUM_CLICKED, load_behaviors
+from .splits import index_split
 
 
-class TrainSet:
+class _TitleRowSet:
+    """What the two training sets share: the corpus titles with the all-zero
+    padding title as their last row (titles_host, titles, min_id, max_id), the
+    device (a bare "cuda" is the current device), the batch shape C, N, L, and
+    batch()'s output buffers. A subclass uploads its own row tables and issues
+    its gather call in _gather."""
+
+    def __init__(self, corpus, C, num_clicked, device):
+        n_news, L = corpus.titles.shape
+        if n_news + 1 > np.iinfo(np.int32).max:
+            raise ValueError("more news than int32 rows address")
+        self.C, self.N, self.L = int(C), int(num_clicked), int(L)
+        self.titles_host = np.concatenate([corpus.titles, np.zeros((1, L), np.int64)])
+        self.max_id = int(self.titles_host.max()) if self.titles_host.size else 0
+        self.min_id = int(self.titles_host.min()) if self.titles_host.size else 0
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._out = {}
+
+    def _upload(self, *names):
+        for name in names:
+            setattr(self, name, torch.from_numpy(getattr(self, name + "_host")).to(self.device))
+
+    def batch(self, sample_idx, *key):
+        """(cand [B, C, L], clicked [B, N, L]) int64 on the set's device. On a
+        GPU: one launch of the set's gather kernel into two buffers this set
+        owns (one pair per batch size; the next call with the same B overwrites
+        them), nothing allocated, no host synchronisation when sample_idx is
+        already an int64 tensor on the device."""
+        if self.device.type != "cuda":
+            return self.host_batch(sample_idx, *key)
+        idx = torch.as_tensor(sample_idx).to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+        B = idx.numel()
+        out = self._out.get(B)
+        if out is None:
+            out = self._out[B] = (torch.empty(B, self.C, self.L, dtype=torch.int64, device=self.device),
+                                  torch.empty(B, self.N, self.L, dtype=torch.int64, device=self.device))
+        self._gather(idx, B, out, *key)
+        return out
+
+
+class TrainSet(_TitleRowSet):
     """behaviors_parsed.tsv as row indices (src/dataset.py:64-85).
 
     titles  int64 [n_news + 1, L]: the corpus titles and one final all-zero
@@ -57,8 +100,7 @@ class TrainSet:
     for the host-assembled baseline route of fit()."""
 
     def __init__(self, behaviors_parsed_path, corpus, num_clicked=NUM_CLICKED, device="cpu"):
-        n_news, L = corpus.titles.shape
-        pad = n_news
+        pad = len(corpus.titles)
         rows = []
         C = None
         with open(behaviors_parsed_path, newline="") as f:
@@ -80,19 +122,9 @@ class TrainSet:
                 rows.append(cand + [pad] * (num_clicked - len(hist)) + hist)
         if not rows:
             raise ValueError(f"{behaviors_parsed_path}: no samples")
-        if n_news + 1 > np.iinfo(np.int32).max:
-            raise ValueError("more news than int32 rows address")
-        self.C, self.N, self.L = C, int(num_clicked), int(L)
+        super().__init__(corpus, C, num_clicked, device)
         self.rows_host = np.asarray(rows, dtype=np.int32).reshape(len(rows), C + self.N)
-        self.titles_host = np.concatenate([corpus.titles, np.zeros((1, L), np.int64)])
-        self.max_id = int(self.titles_host.max()) if self.titles_host.size else 0
-        self.min_id = int(self.titles_host.min()) if self.titles_host.size else 0
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.titles = torch.from_numpy(self.titles_host).to(self.device)
-        self.rows = torch.from_numpy(self.rows_host).to(self.device)
-        self._out = {}
+        self._upload("titles", "rows")
 
     def __len__(self):
         return self.rows_host.shape[0]
@@ -110,24 +142,10 @@ class TrainSet:
         return (torch.from_numpy(np.ascontiguousarray(g[:, :self.C])),
                 torch.from_numpy(np.ascontiguousarray(g[:, self.C:])))
 
-    def batch(self, sample_idx):
-        """(cand [B, C, L], clicked [B, N, L]) int64 on the set's device. On a
-        GPU: one nrms_train_batch_gather launch into two buffers this set owns
-        (one pair per batch size; the next call with the same B overwrites
-        them), nothing allocated, no host synchronisation when sample_idx is
-        already an int64 tensor on the device."""
-        if self.device.type != "cuda":
-            return self.host_batch(sample_idx)
-        idx = torch.as_tensor(sample_idx).to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
-        B = idx.numel()
-        out = self._out.get(B)
-        if out is None:
-            out = self._out[B] = (torch.empty(B, self.C, self.L, dtype=torch.int64, device=self.device),
-                                  torch.empty(B, self.N, self.L, dtype=torch.int64, device=self.device))
+    def _gather(self, idx, B, out):
         N.call("nrms_train_batch_gather", N.ptr(self.titles), self.titles.shape[0], self.L, N.ptr(self.rows),
                len(self), self.C, self.N, N.ptr(idx), B, N.ptr(out[0]), N.ptr(out[1]),
                N.stream_handle(self.device))
-        return out
 
 
 MAX_SAMPLED_NEGATIVES = 15          # the sampler keeps 16 hash slots per sample (16 s + j)
@@ -187,7 +205,7 @@ def draw_positions(seed, epoch, s, n, k):
     return out
 
 
-class ImpressionSet:
+class ImpressionSet(_TitleRowSet):
     """A labelled raw behaviors.tsv as a training set whose negatives are drawn
     anew for every (seed, epoch): what TrainSet holds per sample, kept per
     impression.
@@ -215,39 +233,20 @@ class ImpressionSet:
     out; the reference deals one shuffled negative list out across the
     positives, once, offline."""
 
+    _TABLES = ("titles", "pos_row", "pos_imp", "neg_off", "neg_rows", "imp_hist", "hist_rows")
+
     def __init__(self, behaviors_path, corpus, k=None, num_clicked=NUM_CLICKED, device="cpu"):
         from .config import NRMSConfig
-        from .data import (BehaviorsTable, _index_rows, candidate_rows_numeric, load_behaviors, numeric_news_index,
-                           parse_impression_cells)
-        from .evaluate import history_rows_of, lookup_rows, table_history_rows, users_by_history
         K = int(NRMSConfig.negative_sampling_ratio if k is None else k)
         if not 0 <= K <= MAX_SAMPLED_NEGATIVES:
             raise ValueError(f"K = {K} outside 0..{MAX_SAMPLED_NEGATIVES}")
-        n_news, L = corpus.titles.shape
-        pad = n_news
-        if n_news + 1 > np.iinfo(np.int32).max:
-            raise ValueError("more news than int32 rows address")
-        imps = load_behaviors(behaviors_path)
-        nindex = numeric_news_index(corpus)
         try:
-            if isinstance(imps, BehaviorsTable) and nindex is not None:
-                cand, labels, counts = _index_rows(nindex, imps.cand_num), imps.labels, imps.cand_count
-                imp_hist = imps.hist_user
-                hist_rows = table_history_rows(imps, nindex, num_clicked, pad)
-            else:
-                imps = list(imps)
-                imp_hist, hists = users_by_history(imps)
-                fast = candidate_rows_numeric(imps, nindex)
-                if fast is not None:
-                    cand, labels, counts = fast
-                else:
-                    names, labels, counts = parse_impression_cells(imps)
-                    cand = lookup_rows(corpus, names)
-                hist_rows = history_rows_of(corpus, hists, nindex, num_clicked)
+            split = index_split(corpus, load_behaviors(behaviors_path), num_clicked)
         except KeyError as e:
             raise ValueError(f"{behaviors_path}: unknown news id {e}") from None
-        labels = np.asarray(labels, dtype=np.int64)
-        counts = np.asarray(counts, dtype=np.int64)
+        cand = split.cand
+        labels = np.asarray(split.labels, dtype=np.int64)
+        counts = np.asarray(split.counts, dtype=np.int64)
         if ((labels != 0) & (labels != 1)).any():
             bad = int(labels[(labels != 0) & (labels != 1)][0])
             raise ValueError(f"{behaviors_path}: label {bad}, a training split needs 0/1 labels")
@@ -261,23 +260,16 @@ class ImpressionSet:
             raise ValueError(f"{behaviors_path}: no samples (no positive in an impression with >= {K} negatives)")
         if cand.size > np.iinfo(np.int32).max or I > np.iinfo(np.int32).max:
             raise ValueError("more candidates or impressions than int32 addresses")
-        self.K, self.C, self.N, self.L = K, 1 + K, int(num_clicked), int(L)
+        super().__init__(corpus, 1 + K, num_clicked, device)
+        self.K = K
         self.pos_row_host = cand[keep].astype(np.int32)
         self.pos_imp_host = imp_of[keep].astype(np.int32)
         self.neg_off_host = np.concatenate([[0], np.cumsum(n_neg)]).astype(np.int64)
         self.neg_rows_host = cand[neg].astype(np.int32)
-        self.imp_hist_host = np.asarray(imp_hist, dtype=np.int32)
-        self.hist_rows_host = np.ascontiguousarray(hist_rows, dtype=np.int32).reshape(-1, self.N)
-        self.titles_host = np.concatenate([corpus.titles, np.zeros((1, L), np.int64)])
-        self.max_id = int(self.titles_host.max()) if self.titles_host.size else 0
-        self.min_id = int(self.titles_host.min()) if self.titles_host.size else 0
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        for name in ("titles", "pos_row", "pos_imp", "neg_off", "neg_rows", "imp_hist", "hist_rows"):
-            setattr(self, name, torch.from_numpy(getattr(self, name + "_host")).to(self.device))
-        self._ids, self._imps = corpus.ids, imps           # names, for export_epoch
-        self._out = {}
+        self.imp_hist_host = np.asarray(split.imp_user, dtype=np.int32)
+        self.hist_rows_host = np.ascontiguousarray(split.hist_rows, dtype=np.int32).reshape(-1, self.N)
+        self._upload(*self._TABLES)
+        self._ids, self._imps = corpus.ids, split.impressions           # names, for export_epoch
         self._seed = self._epoch = None
 
     def __len__(self):
@@ -285,8 +277,7 @@ class ImpressionSet:
 
     @property
     def device_bytes(self):
-        return sum(getattr(self, n).numel() * getattr(self, n).element_size()
-                   for n in ("titles", "pos_row", "pos_imp", "neg_off", "neg_rows", "imp_hist", "hist_rows"))
+        return sum(getattr(self, n).numel() * getattr(self, n).element_size() for n in self._TABLES)
 
     def begin_epoch(self, seed, epoch):
         """The (seed, epoch) that batch / host_batch draw with when a call
@@ -355,22 +346,15 @@ class ImpressionSet:
         buffers this set owns (one pair per batch size; the next call with the
         same B overwrites them), nothing allocated, no host synchronisation
         when sample_idx is already an int64 tensor on the device."""
-        seed, epoch = self._key(seed, epoch)
-        if self.device.type != "cuda":
-            return self.host_batch(sample_idx, seed, epoch)
+        return super().batch(sample_idx, *self._key(seed, epoch))
+
+    def _gather(self, idx, B, out, seed, epoch):
         import ctypes
-        idx = torch.as_tensor(sample_idx).to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
-        B = idx.numel()
-        out = self._out.get(B)
-        if out is None:
-            out = self._out[B] = (torch.empty(B, self.C, self.L, dtype=torch.int64, device=self.device),
-                                  torch.empty(B, self.N, self.L, dtype=torch.int64, device=self.device))
         N.call("nrms_train_batch_sample_gather", N.ptr(self.titles), self.titles.shape[0], self.L,
                N.ptr(self.pos_row), N.ptr(self.pos_imp), self.pos_row.shape[0], N.ptr(self.neg_off),
                self.imp_hist.shape[0], N.ptr(self.neg_rows), self.neg_rows.shape[0], N.ptr(self.imp_hist),
                N.ptr(self.hist_rows), self.hist_rows.shape[0], self.K, self.N, N.ptr(idx), B,
                ctypes.c_uint64(seed & _U64), epoch, N.ptr(out[0]), N.ptr(out[1]), N.stream_handle(self.device))
-        return out
 
     def materialize(self, seed, epoch):
         """int32 [S, C + N]: the row table a TrainSet would hold for this

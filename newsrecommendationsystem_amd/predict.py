@@ -35,10 +35,9 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .data import (BehaviorsTable, _index_rows, load_behaviors_any, news_numbers, numeric_news_index,
-                   parse_candidate_cells, read_news_parsed)
-from .evaluate import (history_rows_of, lookup_rows, news_vectors, table_history_rows, user_vectors,
-                       users_by_history)
+from .data import BehaviorsTable, load_behaviors_any, read_news_parsed
+from .evaluate import news_vectors, user_vectors
+from .splits import index_split
 
 TIES = {"order": N.NRMS_RANK_ORDER, "shared": N.NRMS_RANK_SHARED}
 PREDICTION_NAME = "prediction.txt"
@@ -80,34 +79,19 @@ def rank_impressions(news_tab, users, cand_rows, imp_user, offsets, ties="order"
 class PredictPlan:
     """Host-side index arrays of one split for prediction: `cand` (corpus row
     of every candidate), `offsets` [n + 1], `imp_user` [n] (row of hist_rows)
-    and `hist_rows` [users, num_clicked], as EvalPlan builds them, without
-    labels and without the per-pair user array. Takes a BehaviorsTable or a
-    list of Impression, labelled or not (labels are ignored). Ids map through
-    the numeric index when the corpus allows (data.numeric_news_index), else
-    through corpus.index; an unknown id raises KeyError."""
+    and `hist_rows` [users, num_clicked]: splits.index_split's arrays without
+    labels, and the impression ids. Takes a BehaviorsTable or a list of
+    Impression, labelled or not (labels are ignored); an unknown id raises
+    KeyError."""
 
     def __init__(self, corpus, impressions, num_clicked=50):
+        split = index_split(corpus, impressions, num_clicked, labelled=False)
         self.corpus = corpus
         self.num_clicked = num_clicked
         self.impressions = impressions
-        pad = len(corpus)
-        nindex = numeric_news_index(corpus)
-        if isinstance(impressions, BehaviorsTable) and nindex is not None:
-            tab = impressions
-            self.cand = _index_rows(nindex, tab.cand_num)
-            counts = tab.cand_count
-            self.imp_user = np.ascontiguousarray(tab.hist_user, dtype=np.int64)
-            self.hist_rows = table_history_rows(tab, nindex, num_clicked, pad)
-            self.impression_ids = [tab.text[a:b] for a, b in tab.fields[:, 0].tolist()]
-        else:
-            imps = list(impressions)
-            self.imp_user, hists = users_by_history(imps)
-            names, counts = parse_candidate_cells(imps)
-            nums = news_numbers(names) if nindex is not None else None
-            self.cand = _index_rows(nindex, nums) if nums is not None else lookup_rows(corpus, names)
-            self.hist_rows = history_rows_of(corpus, hists, nindex, num_clicked)
-            self.impression_ids = [im.impression_id for im in imps]
-        self.offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        self.cand, self.offsets = split.cand, split.offsets
+        self.imp_user, self.hist_rows = split.imp_user, split.hist_rows
+        self.impression_ids = split.impression_ids()
 
     @property
     def n_impressions(self):
@@ -364,15 +348,8 @@ def main(argv=None):
         return 0
     if not a.directory or not a.checkpoint:
         ap.error("DIR and --checkpoint are required")
-    from . import checkpoint as CK
-    from .config import NRMSConfig
-    from .nrms import NRMS
-    state = CK.load(a.checkpoint)["model_state_dict"]
-    V, D = state["news_encoder.word_embedding.weight"].shape
-    cfg = type("PredictCfg", (NRMSConfig,), dict(num_words=int(V), word_embedding_dim=int(D)))
-    model = NRMS(cfg)
-    model.load_state_dict(state)
-    model = model.to(torch.device("cuda:0")).eval()
+    from .checkpoint import load_model
+    model = load_model(a.checkpoint, "cuda:0")
     corpus = read_news_parsed(os.path.join(a.directory, "news_parsed.tsv"))
     imps = load_behaviors_any(os.path.join(a.directory, "behaviors.tsv"))
     write_prediction(a.out, predict_split(model, corpus, imps, a.ties), zip=a.zip)

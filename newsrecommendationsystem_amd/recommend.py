@@ -30,9 +30,9 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .data import (PADDED_NEWS, BehaviorsTable, history_ids, history_rows_numeric, load_behaviors,
-                   numeric_news_index, read_news_parsed)
+from .data import BehaviorsTable, load_behaviors, read_news_parsed
 from .evaluate import news_vectors, user_vectors
+from .splits import history_rows_of as history_rows   # (corpus, hists, num_clicked): EvalPlan's hist_rows
 
 MAX_K = 256
 MAX_EXCLUDE = 256
@@ -123,20 +123,6 @@ def first_lines(impressions):
             users.append(im.user)
             hists.append(im.clicked_news)
     return users, hists
-
-
-def history_rows(corpus, hists, num_clicked):
-    """[len(hists), num_clicked] corpus rows of each history's first
-    num_clicked ids, left-padded with len(corpus) (the PADDED_NEWS row):
-    EvalPlan's hist_rows for these strings. An unknown id raises KeyError."""
-    pad = len(corpus)
-    rows = history_rows_numeric(hists, numeric_news_index(corpus), num_clicked, pad)
-    if rows is not None:
-        return rows
-    names = [x for h in hists for x in history_ids(h, num_clicked)]
-    flat = np.fromiter((pad if x == PADDED_NEWS else corpus.index[x] for x in names), dtype=np.int64,
-                       count=len(names))
-    return flat.reshape(len(hists), num_clicked)
 
 
 @torch.no_grad()
@@ -291,15 +277,8 @@ def main(argv=None):
         return 0
     if not a.directory or not a.checkpoint:
         ap.error("DIR and --checkpoint are required")
-    from . import checkpoint as CK
-    from .config import NRMSConfig
-    from .nrms import NRMS
-    state = CK.load(a.checkpoint)["model_state_dict"]
-    V, D = state["news_encoder.word_embedding.weight"].shape
-    cfg = type("RecommendCfg", (NRMSConfig,), dict(num_words=int(V), word_embedding_dim=int(D)))
-    model = NRMS(cfg)
-    model.load_state_dict(state)
-    model = model.to(torch.device("cuda:0")).eval()
+    from .checkpoint import load_model
+    model = load_model(a.checkpoint, "cuda:0")
     corpus = read_news_parsed(os.path.join(a.directory, "news_parsed.tsv"))
     imps = load_behaviors(os.path.join(a.directory, "behaviors.tsv"))
     if a.user is not None:

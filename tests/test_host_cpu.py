@@ -39,7 +39,7 @@ REF_KEYS = [
 def _declared_functions():
     src = open(HEADER).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(nrms_[a-z_]+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b(nrms_[a-z0-9_]+)\s*\(", src)))
 
 
 def test_library_built():
