@@ -11,8 +11,9 @@
  *
  * Conventions
  *   - All tensor arguments are caller-allocated DEVICE pointers, borrowed for
- *     the call (except nrms_adam_step_multi's descriptor array, a HOST array
- *     read during the call). The library never allocates or frees device
+ *     the call (except the descriptor arrays of nrms_adam_step_multi,
+ *     nrms_params_pack and nrms_params_unpack_div: HOST arrays read during
+ *     the call). The library never allocates or frees device
  *     memory and never synchronises the stream; any host thread may call it
  *     on any stream, and every call is capturable into a hipGraph. It keeps
  *     no per-call state. Process-wide state is limited to: the GEMM
@@ -700,6 +701,34 @@ int32_t nrms_train_batch_sample_gather(const int64_t* titles, int64_t n_title_ro
  * batches (B in the hundreds), not for scoring a split. */
 int32_t nrms_xent_class0(const float* logits, int64_t B, int32_t C,
                          float* dlogits, float* loss_out, hipStream_t stream);
+
+/* (ABI 9, added later) The FedAvg exchange's two copies (csrc/fedavg.hip):
+ * n parameters to and from one contiguous fp32 buffer, the buffer an
+ * all-reduce sums. `offset` counts floats into flat.
+ *   nrms_params_pack:        flat[offset_t + i] = data_t[i]
+ *   nrms_params_unpack_div:  data_t[i] = flat[offset_t + i] / divisor
+ * for 0 <= i < numel_t. The quotient is the correctly rounded IEEE fp32
+ * division (numpy.float32(x) / numpy.float32(divisor), subnormals kept), not a
+ * reciprocal multiply; divisor 1 copies the bits. `tensors` is a HOST array
+ * read during the call; up to 32 descriptors go to the device by value in one
+ * launch's arguments (ceil(n / 32) launches). 16-byte loads and stores where a
+ * tensor's base and its place in flat are both 16-byte aligned, scalar
+ * otherwise and for the last numel % 4 floats: neither alignment nor numel % 4
+ * matters for the result. flat must hold max_t(offset_t + numel_t) floats;
+ * ranges must not overlap. Nothing allocated, no host synchronisation,
+ * graph-capturable. numel == 0 is skipped; n == 0: NRMS_OK, nothing launched.
+ * NRMS_ERR_INVALID_ARG, nothing launched: n < 0, a null `tensors` with n > 0,
+ * numel < 0 or offset < 0, a null data or flat pointer with numel > 0, a
+ * divisor that is 0 or NaN. */
+typedef struct {
+  float* data;
+  int64_t numel;
+  int64_t offset;
+} nrms_flat_tensor_t;
+
+int32_t nrms_params_pack(const nrms_flat_tensor_t* tensors, int32_t n, float* flat, hipStream_t stream);
+int32_t nrms_params_unpack_div(const nrms_flat_tensor_t* tensors, int32_t n, const float* flat,
+                               float divisor, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Host-side readers of the eval split (csrc/tsv_io.hip). HOST pointers, no

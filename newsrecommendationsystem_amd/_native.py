@@ -43,6 +43,11 @@ class ForwardState(ctypes.Structure):
 
 
 _FS = ctypes.POINTER(ForwardState)
+
+
+class FlatTensor(ctypes.Structure):
+    """nrms_flat_tensor_t: one parameter and its place (in floats) in the flat buffer."""
+    _fields_ = [("data", _p), ("numel", _i64), ("offset", _i64)]
 NRMS_STATE_FOLDED_TABLE, NRMS_STATE_QKV_PACKS, NRMS_STATE_ADD_PACKS = 1, 2, 4
 
 # name -> (restype, argtypes)
@@ -100,6 +105,9 @@ SIGNATURES = {
                               ctypes.c_float, _i64, _p]),
     "nrms_adam_step_multi": (_i32, [_p, _i32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                     ctypes.c_float, _i64, _p]),
+    # FedAvg exchange (train.FedAvg): host descriptor array, n, flat, [divisor,] stream
+    "nrms_params_pack": (_i32, [_p, _i32, _p, _p]),
+    "nrms_params_unpack_div": (_i32, [_p, _i32, _p, ctypes.c_float, _p]),
     # fit loop (fit.py)
     "nrms_train_batch_gather": (_i32, [_p, _i64, _i32, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p]),
     "nrms_train_batch_sample_gather": (_i32, [_p, _i64, _i32, _p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64,

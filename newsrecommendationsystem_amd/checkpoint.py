@@ -84,6 +84,45 @@ def resume(path, model, optimizer=None):
     return int(ck["step"]), ck["early_stop_value"]
 
 
+def rank_path(path, rank):
+    """ckpt-{t}.rank{r}.pth beside ckpt-{t}.pth: client r's own optimizer
+    state of a federated fit (fit.fit(fed=...)). latest_checkpoint skips such
+    names: their second-to-last dotted part is no step number."""
+    root, ext = os.path.splitext(path)
+    return f"{root}.rank{int(rank)}{ext}"
+
+
+def save_rank(path, rank, optimizer, step):
+    """Client `rank` > 0's file beside the checkpoint `path`: its optimizer
+    state and the step, nothing else (the model is rank 0's file's)."""
+    torch.save({"optimizer_state_dict": optimizer.state_dict(), "step": int(step)}, rank_path(path, rank))
+
+
+def _load_optimizer(optimizer, state):
+    optimizer.load_state_dict(state)
+    for st in optimizer.state.values():
+        step = st.get("step")
+        if torch.is_tensor(step) and step.device.type != "cpu":
+            st["step"] = step.cpu()
+
+
+def resume_rank(path, rank, model, optimizer):
+    """resume() for client `rank` > 0 of a federated fit: the model from
+    `path`, the optimizer from rank_path(path, rank) when that file exists and
+    holds the same step, else from `path` (rank 0's moments: the world size
+    changed, or the file was lost). Returns (step, early_stop_value, whether
+    the rank's own file was used)."""
+    ck = load(path, map_location="cpu")
+    model.load_state_dict(ck["model_state_dict"])
+    own = None
+    if os.path.exists(rank_path(path, rank)):
+        own = load(rank_path(path, rank), map_location="cpu")
+        if int(own["step"]) != int(ck["step"]):
+            own = None
+    _load_optimizer(optimizer, (own or ck)["optimizer_state_dict"])
+    return int(ck["step"]), ck["early_stop_value"], own is not None
+
+
 def save(path, model, optimizer, step, early_stop_value):
     """src/train.py:266-277."""
     torch.save({"model_state_dict": model.state_dict(),

@@ -1170,4 +1170,26 @@ int32_t nrms_adam_step_multi(const nrms_adam_tensor_t* tensors, int32_t n, float
   return launch_adam_multi(tensors, n, lr, beta1, beta2, eps, step, stream);
 }
 
+static int32_t check_flat_tensors(const nrms_flat_tensor_t* tensors, int32_t n, const float* flat) {
+  if (n < 0 || (n > 0 && !tensors)) return NRMS_ERR_INVALID_ARG;
+  for (int32_t i = 0; i < n; ++i) {
+    const nrms_flat_tensor_t& t = tensors[i];
+    if (t.numel < 0 || t.offset < 0) return NRMS_ERR_INVALID_ARG;
+    if (t.numel > 0 && (!t.data || !flat)) return NRMS_ERR_INVALID_ARG;
+  }
+  return NRMS_OK;
+}
+
+int32_t nrms_params_pack(const nrms_flat_tensor_t* tensors, int32_t n, float* flat, hipStream_t stream) {
+  if (int32_t st = check_flat_tensors(tensors, n, flat)) return st;
+  return launch_params_pack(tensors, n, flat, stream);
+}
+
+int32_t nrms_params_unpack_div(const nrms_flat_tensor_t* tensors, int32_t n, const float* flat,
+                               float divisor, hipStream_t stream) {
+  if (divisor == 0.0f || divisor != divisor) return NRMS_ERR_INVALID_ARG;     // 0 and NaN
+  if (int32_t st = check_flat_tensors(tensors, n, flat)) return st;
+  return launch_params_unpack_div(tensors, n, flat, divisor, stream);
+}
+
 }  // extern "C"

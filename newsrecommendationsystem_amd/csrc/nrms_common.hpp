@@ -362,6 +362,11 @@ int32_t launch_adam_multi(const nrms_adam_tensor_t* ts, int n, float lr, float b
                           float eps, int64_t step, hipStream_t s);
 int32_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1,
                     float b2, float eps, int64_t step, hipStream_t s);
+// FedAvg exchange (fedavg.hip); the contracts are nrms_params_pack's and
+// nrms_params_unpack_div's (nrms_hip.h)
+int32_t launch_params_pack(const nrms_flat_tensor_t* ts, int n, float* flat, hipStream_t s);
+int32_t launch_params_unpack_div(const nrms_flat_tensor_t* ts, int n, const float* flat, float divisor,
+                                 hipStream_t s);
 // fit loop kernels (fit.hip); the contracts are nrms_train_batch_gather's and
 // nrms_xent_class0's (nrms_hip.h)
 int32_t launch_train_batch_gather(const int64_t* titles, int64_t n_title_rows, int L, const int32_t* sample_rows,

@@ -57,6 +57,20 @@ def all_reduce_(t, group=None):
     return t
 
 
+def broadcast_(t, src=0, group=None):
+    """In-place broadcast of rank `src`'s tensor (`src`: a rank of `group`); a
+    CUDA tensor under gloo goes through host memory, as all_reduce_ does."""
+    import torch.distributed as dist
+    gsrc = src if group is None else dist.get_global_rank(group, src)
+    if t.is_cuda and dist.get_backend(group) == "gloo":
+        host = t.cpu()
+        dist.broadcast(host, gsrc, group=group)
+        t.copy_(host)
+    else:
+        dist.broadcast(t, gsrc, group=group)
+    return t
+
+
 def _reduce_scalar(x, device, op, group=None):
     """One fp64 scalar reduced over the group: on the device under RCCL
     ("nccl"), through host memory under gloo."""

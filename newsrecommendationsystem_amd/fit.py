@@ -27,6 +27,12 @@ function of (seed, e, S) and the dropout seed one of (seed, step), so a resumed
 run continues the trajectory of an uninterrupted one; and a resumed run stops
 at the same total step count (the reference restarts its counter and trains
 num_epochs more).
+
+fit(fed=train.FedAvg(...)) is the same loop as one client of a federation
+(BASELINE config 5): each rank trains on the samples of the users it owns and
+the models are averaged on a schedule that is a function of the step alone
+(sync_due); validation is sharded by user, checkpoints are per rank (fit's
+docstring; DESIGN §Federated fit).
 """
 import csv
 import os
@@ -97,7 +103,9 @@ class TrainSet(_TitleRowSet):
     collate stacks them); the `clicked` column is read and ignored
     (src/train.py:205 trains against class 0). ValueError on a ragged line or
     an unknown news id. Host copies (titles_host, rows_host) stay available
-    for the host-assembled baseline route of fit()."""
+    for the host-assembled baseline route of fit(). users: the `user` column,
+    one name per sample (None when the file has no such column; only a
+    federated fit, which shards by user, needs it)."""
 
     def __init__(self, behaviors_parsed_path, corpus, num_clicked=NUM_CLICKED, device="cpu"):
         pad = len(corpus.titles)
@@ -108,7 +116,11 @@ class TrainSet(_TitleRowSet):
             header = next(rd)
             cc, cn = header.index("clicked_news"), header.index("candidate_news")
             header.index("clicked")          # must be there; its values are not used
+            cu = header.index("user") if "user" in header else None
+            users = [] if cu is not None else None
             for k, row in enumerate(rd):
+                if users is not None:
+                    users.append(row[cu])
                 try:
                     cand = [corpus.index[x] for x in row[cn].split()]
                     hist = [corpus.index[x] for x in row[cc].split()[:num_clicked]]
@@ -124,6 +136,7 @@ class TrainSet(_TitleRowSet):
             raise ValueError(f"{behaviors_parsed_path}: no samples")
         super().__init__(corpus, C, num_clicked, device)
         self.rows_host = np.asarray(rows, dtype=np.int32).reshape(len(rows), C + self.N)
+        self.users = users
         self._upload("titles", "rows")
 
     def __len__(self):
@@ -272,6 +285,13 @@ class ImpressionSet(_TitleRowSet):
         self._ids, self._imps = corpus.ids, split.impressions           # names, for export_epoch
         self._seed = self._epoch = None
 
+    @property
+    def users(self):
+        """Each sample's user: its impression's."""
+        from .data import BehaviorsTable
+        u = self._imps.users() if isinstance(self._imps, BehaviorsTable) else [im.user for im in self._imps]
+        return [u[i] for i in self.pos_imp_host.tolist()]
+
     def __len__(self):
         return self.pos_row_host.shape[0]
 
@@ -367,12 +387,11 @@ class ImpressionSet(_TitleRowSet):
         """Write the epoch's samples as a behaviors_parsed.tsv
         (data.write_behaviors_parsed): what TrainSet and the reference's
         BaseDataset read."""
-        from .data import BehaviorsTable, write_behaviors_parsed
+        from .data import write_behaviors_parsed
         rows = self.materialize(seed, epoch)
         pad = self.titles_host.shape[0] - 1
         ids = self._ids
-        users = self._imps.users() if isinstance(self._imps, BehaviorsTable) else [im.user for im in self._imps]
-        write_behaviors_parsed(path, [users[i] for i in self.pos_imp_host.tolist()],
+        write_behaviors_parsed(path, self.users,
                                [[ids[r] for r in h if r != pad] for h in rows[:, self.C:].tolist()],
                                [[ids[r] for r in c] for c in rows[:, :self.C].tolist()],
                                [[1] + [0] * self.K] * len(self))
@@ -414,6 +433,56 @@ def batch_of_step(step, S, batch_size):
     return e, k * batch_size, (k + 1) * batch_size
 
 
+def client_seed(seed, rank):
+    """Seed of federated client `rank`: `seed` itself for rank 0 (a federation
+    of one is the plain fit), else mix64(mix64(seed) + rank) mod 2^62: the
+    client's epoch orders and dropout masks are epoch_order(client_seed, e,
+    S_r) and dropout_seed(client_seed, t)."""
+    if int(rank) == 0:
+        return int(seed)
+    return mix64((mix64(int(seed) & _U64) + int(rank)) & _U64) & (2 ** 62 - 1)
+
+
+def sample_owners(train_set, world):
+    """int64 [S]: the client that owns each sample of `train_set`, its user's
+    distributed.user_rank. ValueError when the set carries no users (a
+    behaviors_parsed.tsv without the `user` column)."""
+    from .distributed import user_rank
+    users = train_set.users
+    if users is None:
+        raise ValueError("a federated fit shards the samples by user: behaviors_parsed.tsv has no `user` column")
+    owner = {}
+    return np.fromiter((owner[u] if u in owner else owner.setdefault(u, user_rank(u, world)) for u in users),
+                       dtype=np.int64, count=len(users))
+
+
+def client_shard(train_set, rank, world):
+    """int64 [S_r]: the samples of `train_set`, ascending, that client `rank`
+    of `world` owns."""
+    return np.flatnonzero(sample_owners(train_set, world) == rank).astype(np.int64)
+
+
+def shard_sizes(train_set, world):
+    """[S_0, .., S_{world-1}]: every client's sample count (each rank computes
+    all of them from the users it loaded; no collective)."""
+    return np.bincount(sample_owners(train_set, world), minlength=world).tolist()
+
+
+def federated_total_steps(num_epochs, S_total, world, batch_size):
+    """Global steps of a federated fit: num_epochs epochs of an average shard
+    (S_total // world samples), the same number on every rank; each client
+    wraps its own epochs (batch_of_step on its S_r)."""
+    return num_epochs * (S_total // world) // batch_size
+
+
+def sync_due(t, every, validate_every, last):
+    """Whether the clients average their models after global step t: every
+    `every` steps, before a validation (t % validate_every == 0; 0: none) and
+    after the last step. A function of t alone, so a resumed run syncs where
+    the uninterrupted one does."""
+    return (every > 0 and t % every == 0) or (validate_every > 0 and t % validate_every == 0) or t == last
+
+
 class EarlyStopping:
     """src/train.py:27-51: called with -AUC; strict <."""
 
@@ -444,6 +513,8 @@ class FitResult:
     early_stopped: bool = False
     best_loss: float = np.inf      # EarlyStopping's value (-best AUC)
     optimizer: object = None
+    syncs: int = 0                 # federated fit: model averagings of this call (the start broadcast not counted)
+    shard_sizes: list = None       # federated fit: every client's sample count
 
     @property
     def last_auc(self):
@@ -456,10 +527,17 @@ class FitResult:
 
 class _DirValidator:
     """evaluate(model, val_dir, max_count=200000)'s AUC (src/train.py:248-250)
-    with the split read and indexed once (EvalPlan), scored each time."""
+    with the split read and indexed once (EvalPlan), scored each time.
 
-    def __init__(self, directory, num_clicked):
+    sharded (a federated fit; `group` its process group, None: the default
+    one): max_count cuts the global impression list first, this rank scores
+    the impressions of the users it owns (distributed.shard_impressions) and
+    the metric sums are all-reduced, so every rank returns the same AUC from
+    the same reduced buffer."""
+
+    def __init__(self, directory, num_clicked, group=None, sharded=False, max_count=200000):
         self.directory, self.num_clicked, self.plan = directory, num_clicked, None
+        self.group, self.sharded, self.max_count = group, sharded, max_count
 
     def __call__(self, model):
         from .data import load_behaviors, read_news_parsed
@@ -467,13 +545,29 @@ class _DirValidator:
         if self.plan is None:
             corpus = read_news_parsed(os.path.join(self.directory, "news_parsed.tsv"))
             imps = load_behaviors(os.path.join(self.directory, "behaviors.tsv"))
-            self.plan = EvalPlan(corpus, imps, max_count=200000, num_clicked=self.num_clicked)
-        _, metrics = score_plan(model, self.plan)
-        return reduce_means(*nan_sums(metrics))[0]
+            if self.sharded:
+                import torch.distributed as dist
+
+                from .distributed import shard_impressions
+                n = len(imps) if self.max_count > len(imps) else max(0, self.max_count - 1)   # EvalPlan's cut
+                imps = shard_impressions(imps[:n], dist.get_rank(self.group), dist.get_world_size(self.group))
+                self.plan = EvalPlan(corpus, imps, num_clicked=self.num_clicked)
+            else:
+                self.plan = EvalPlan(corpus, imps, max_count=self.max_count, num_clicked=self.num_clicked)
+        if not self.sharded:
+            _, metrics = score_plan(model, self.plan)
+            return reduce_means(*nan_sums(metrics))[0]
+        from .distributed import all_reduce_sums
+        if self.plan.n_impressions:
+            sums, counts = nan_sums(score_plan(model, self.plan)[1])
+        else:
+            dev = next(model.parameters()).device
+            sums, counts = (torch.zeros(4, dtype=torch.float64, device=dev) for _ in range(2))
+        return reduce_means(*all_reduce_sums(sums, counts, self.group))[0]
 
 
 def fit(model, train_set, val=None, *, checkpoint_dir=None, seed=0, steps=None, batch_size=None,
-        validate=None, log=print, host_batches=False):
+        validate=None, log=print, host_batches=False, fed=None):
     """The reference's train() on `train_set` (module docstring): a TrainSet
     (the file's static negatives), or an ImpressionSet, whose negatives epoch
     e draws with the loop's (seed, e) -- told through begin_epoch. `validate`:
@@ -482,11 +576,42 @@ def fit(model, train_set, val=None, *, checkpoint_dir=None, seed=0, steps=None, 
     steps this call runs (default: up to num_epochs * S // batch_size in
     total, counting a resumed checkpoint's). host_batches: the baseline route
     on a GPU (batches assembled on the host and uploaded, torch's loss
-    kernels, loss.item() every step). Returns a FitResult."""
+    kernels, loss.item() every step). Returns a FitResult.
+
+    fed (a train.FedAvg over this model): the call is one client of a
+    federation, made by every rank of fed's group with the same arguments.
+    The client trains on the samples whose user it owns (client_shard: a
+    device table of global sample indices, applied to the epoch's order on the
+    device; an ImpressionSet still draws with (seed, epoch, global sample)),
+    with client_seed(seed, rank) for its epoch orders and dropout masks; t is
+    global, the default total federated_total_steps(...) - start step. The
+    clients start from rank 0's model (fed.broadcast after an optional resume)
+    and average theirs where sync_due says; Adam moments stay local. A `val`
+    directory is scored sharded by user with the metric sums all-reduced (a
+    `validate` callable must return the same value on every rank), so every
+    rank takes the same early-stopping decisions. Rank 0 writes ckpt-{t}.pth
+    (the averaged model, its own optimizer state), rank r > 0 its optimizer
+    state to ckpt-{t}.rank{r}.pth; a resuming rank without its file takes rank
+    0's moments and logs that. Log lines come from rank 0. ValueError: a set
+    without users, a shard smaller than the batch (the rank is named),
+    host_batches."""
     cfg = model.config
     dev = next(model.parameters()).device
     B = int(batch_size if batch_size is not None else cfg.batch_size)
     S = len(train_set)
+    rank, world, owned, cseed = 0, 1, None, seed
+    if fed is not None:
+        if host_batches:
+            raise ValueError("host_batches is the single-client baseline route: not with fed")
+        rank, world = fed.dist.get_rank(fed.group), fed.world
+        owners = sample_owners(train_set, world)                   # raises without users
+        sizes = np.bincount(owners, minlength=world).tolist()
+        owned = np.flatnonzero(owners == rank).astype(np.int64)
+        for r, n in enumerate(sizes):                              # every rank raises, naming the short one
+            if B > 0 and n < B:
+                raise ValueError(f"rank {r}: its shard of {n} samples (of {S}, world {world}) is smaller than "
+                                 f"the batch size {B}")
+        S_total, S, cseed = S, int(owned.size), client_seed(seed, rank)
     if B <= 0 or S // B == 0:
         raise ValueError(f"batch size {B} leaves no full batch of {S} samples (drop_last)")
     if train_set.min_id < 0 or train_set.max_id >= cfg.num_words:
@@ -501,18 +626,33 @@ def fit(model, train_set, val=None, *, checkpoint_dir=None, seed=0, steps=None, 
     optimizer = TR.make_optimizer(model)
     early = EarlyStopping()
     res = FitResult(optimizer=optimizer)
+    say = log if rank == 0 else (lambda *_: None)
     if checkpoint_dir is not None:
         os.makedirs(checkpoint_dir, exist_ok=True)
+        if fed is not None and world > 1:
+            fed.dist.barrier(group=fed.group)             # files an earlier call of another rank still writes
         path = CK.latest_checkpoint(checkpoint_dir)
         if path is not None:
-            log(f"Load saved parameters in {path}")
-            res.start_step, esv = CK.resume(path, model, optimizer)
+            say(f"Load saved parameters in {path}")
+            if rank == 0:
+                res.start_step, esv = CK.resume(path, model, optimizer)
+            else:
+                res.start_step, esv, own = CK.resume_rank(path, rank, model, optimizer)
+                if not own:
+                    log(f"rank {rank}: no {os.path.basename(CK.rank_path(path, rank))}, "
+                        f"taking rank 0's optimizer state")
             early(esv)                                    # src/train.py:148
             res.checkpoint = path
     if validate is None and val is not None:
-        validate = _DirValidator(val, cfg.num_clicked_news_a_user)
+        validate = _DirValidator(val, cfg.num_clicked_news_a_user, group=fed.group if fed is not None else None,
+                                 sharded=fed is not None)
     if steps is None:
-        steps = max(0, cfg.num_epochs * S // B - res.start_step)
+        total = cfg.num_epochs * S // B if fed is None else federated_total_steps(cfg.num_epochs, S_total, world, B)
+        steps = max(0, total - res.start_step)
+    if fed is not None:
+        fed.broadcast(0)                                  # one model, whatever each rank was seeded with
+        res.shard_sizes = sizes
+        owned = torch.from_numpy(owned).to(dev)
     model.train()
 
     show, every = int(cfg.num_batches_show_loss), int(cfg.num_batches_validate)
@@ -532,17 +672,20 @@ def fit(model, train_set, val=None, *, checkpoint_dir=None, seed=0, steps=None, 
         torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     t = res.start_step
-    for t in range(res.start_step + 1, res.start_step + steps + 1):
+    last = res.start_step + steps
+    for t in range(res.start_step + 1, last + 1):
         e, a, b = batch_of_step(t, S, B)
         if e != epoch:
-            epoch, order = e, epoch_order(seed, e, S)
+            epoch, order = e, epoch_order(cseed, e, S)
             if begin_epoch is not None:
                 begin_epoch(seed, e)
             if dev.type == "cuda" and not host_batches:
                 order = order.to(dev)
+            if owned is not None:
+                order = owned[order]                      # local -> global sample, on the device
         if host_batches:
             cand, clk = train_set.host_batch(order[a:b])
-            logits = train_hip.forward_hip(model, cand.to(dev), clk.to(dev), seed=dropout_seed(seed, t))
+            logits = train_hip.forward_hip(model, cand.to(dev), clk.to(dev), seed=dropout_seed(cseed, t))
             loss = TR.loss_fn(logits)
             optimizer.zero_grad()
             loss.backward()
@@ -554,7 +697,7 @@ def fit(model, train_set, val=None, *, checkpoint_dir=None, seed=0, steps=None, 
             slot = t % loss_log.numel()
             cand, clk = train_set.batch(order[a:b])
             if hip:
-                logits = train_hip.forward_hip(model, cand, clk, seed=dropout_seed(seed, t))
+                logits = train_hip.forward_hip(model, cand, clk, seed=dropout_seed(cseed, t))
                 _, dlogits = xent_class0(logits.detach(), loss_out=loss_log[slot:slot + 1])
                 optimizer.zero_grad()
                 logits.backward(dlogits)
@@ -562,9 +705,12 @@ def fit(model, train_set, val=None, *, checkpoint_dir=None, seed=0, steps=None, 
             else:
                 loss_log[slot].copy_(TR.train_step(model, optimizer, cand, clk))
             pending.append(slot)
+        if fed is not None and sync_due(t, fed.every, every if validate is not None else 0, last):
+            fed.sync()
+            res.syncs += 1
         if show > 0 and t % show == 0:
             flush()
-            log(f"batches {t}, current loss {losses[-1]:.4f}, average loss: {np.mean(losses):.4f}, "
+            say(f"batches {t}, current loss {losses[-1]:.4f}, average loss: {np.mean(losses):.4f}, "
                 f"latest average loss: {np.mean(losses[-256:]):.4f}")        # src/train.py:241-244
         if validate is not None and every > 0 and t % every == 0:
             flush()
@@ -572,15 +718,18 @@ def fit(model, train_set, val=None, *, checkpoint_dir=None, seed=0, steps=None, 
             auc = float(validate(model))
             model.train()
             res.aucs.append((t, auc))
-            log(f"batches {t}, validation AUC: {auc:.4f}")
+            say(f"batches {t}, validation AUC: {auc:.4f}")
             stop, better = early(-auc)
             if stop:
-                log("Early stop.")
+                say("Early stop.")
                 res.early_stopped = True
                 break
             if better and checkpoint_dir is not None:
                 res.checkpoint = os.path.join(checkpoint_dir, f"ckpt-{t}.pth")
-                CK.save(res.checkpoint, model, optimizer, t, -auc)
+                if rank == 0:
+                    CK.save(res.checkpoint, model, optimizer, t, -auc)
+                else:
+                    CK.save_rank(res.checkpoint, rank, optimizer, t)
     flush()
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
