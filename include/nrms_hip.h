@@ -547,7 +547,10 @@ int32_t nrms_forward_prepared_timed(const int64_t* cand_ids, const int64_t* clic
  * Python glue (newsrecommendationsystem_amd/train_hip.py) chains them in a
  * torch.autograd.Function. Gradient outputs named d_* are ACCUMULATED into
  * (callers zero them), dx / dqkv / dnews outputs are overwritten. fp32; the
- * GEMMs of the backward use f32 MFMA whatever nrms_set_gemm_arith says. */
+ * GEMMs of the backward (dx = dY W and dW += dY^T X) run on split-bf16 x6
+ * under both split modes of nrms_set_gemm_arith and on f32 MFMA under
+ * NRMS_GEMM_F32 (dW also when dY or X is not 16-byte aligned); the GEMM of
+ * nrms_additive_forward_train is f32 MFMA in every mode. */
 
 /* F.dropout(x, p, training=True) (news_encoder.py:38-40,43-45): y[i] = x[i] /
  * (1-p) if u(seed, i) >= p else 0, u a counter-based uniform (splitmix64 of
