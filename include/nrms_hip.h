@@ -384,8 +384,17 @@ int32_t nrms_recommend_topk(const float* news, int64_t n_news, const float* user
  * score or an empty impression: all four NaN (roc_auc_score raises, the
  * reference's ValueError branch). One class only: AUC NaN (scikit-learn >= 1.3
  * warns instead of raising) and MRR / nDCG as numpy computes them (all
- * negative: NaN; all positive: MRR = mean(1/rank), nDCG = 1). Ranking order = np.argsort(score)[::-1]: descending,
- * equal scores by larger index first. */
+ * negative: NaN; all positive: MRR = mean(1/rank), nDCG = 1).
+ *   - Tie order. The ranking is np.argsort(score, kind="stable")[::-1]:
+ *     descending score, and among equal scores (-0 == +0) the candidate with
+ *     the LARGER index first: rank_c = 1 + #{j : s_j > s_c or (s_j == s_c and
+ *     j > c)}, the order nrms_rank_impressions calls NRMS_RANK_ORDER. MRR and
+ *     both nDCGs follow that order, so a positive tied with a later negative
+ *     ranks after it; AUC counts a positive tied with a negative as 1/2.
+ *   - offsets[n_imp + 1] are ABSOLUTE positions into scores / labels,
+ *     non-decreasing; offsets[0] need not be 0 (elements before it belong to
+ *     no impression and are never read), and offsets[i] == offsets[i + 1] is
+ *     an empty impression (a NaN row). */
 int32_t nrms_impression_metrics(const float* scores, const int32_t* labels,
                                 const int64_t* offsets, int64_t n_imp, double* out,
                                 hipStream_t stream);
