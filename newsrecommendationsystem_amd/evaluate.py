@@ -18,14 +18,26 @@ host:
      nanmean (evaluate.py:270-272) — or, across ranks, an all-reduce of
      (sum, count) per metric.
 """
+import os
 import sys
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from . import _native as N
 from .data import load_behaviors, read_news_parsed
+from .distributed import all_reduce_sums, shard_impressions
 from .splits import index_split
+
+
+def cut_impressions(impressions, max_count=sys.maxsize):
+    """The impressions the reference scores under max_count: it counts from 1
+    and breaks when count == max_count before scoring that one
+    (src/evaluate.py:245-249), so impressions 1..max_count-1; all of them when
+    the count never reaches max_count (above their number, or below 1). The
+    list itself when nothing is cut."""
+    return impressions if not 1 <= max_count <= len(impressions) else impressions[:max_count - 1]
 
 
 class EvalPlan:
@@ -35,10 +47,7 @@ class EvalPlan:
     KeyError as news2vector[...] does."""
 
     def __init__(self, corpus, impressions, max_count=sys.maxsize, num_clicked=50):
-        # the reference breaks when count == max_count before scoring it
-        # (src/evaluate.py:245-249): impressions 1..max_count-1 are scored
-        n = len(impressions) if max_count > len(impressions) else max(0, max_count - 1)
-        split = index_split(corpus, impressions if n == len(impressions) else impressions[:n], num_clicked)
+        split = index_split(corpus, cut_impressions(impressions, max_count), num_clicked)
         self.corpus = corpus
         self.num_clicked = num_clicked
         self.impressions = split.impressions
@@ -120,6 +129,22 @@ def reduce_means(sums, counts):
 
 
 @torch.no_grad()
+def evaluate_plan(model, plan, process_group=None):
+    """(AUC, MRR, nDCG@5, nDCG@10) of `plan`: the nanmean of score_plan's
+    metric table (src/evaluate.py:270-272). With a `process_group`, `plan` is
+    this rank's shard (it may be empty) and the (sum, count) per metric are
+    all-reduced: every rank returns the same means."""
+    if plan.n_impressions:
+        sums, counts = nan_sums(score_plan(model, plan)[1])
+    else:
+        dev = model.news_encoder.word_embedding.weight.device
+        sums, counts = (torch.zeros(4, dtype=torch.float64, device=dev) for _ in range(2))
+    if process_group is not None:
+        sums, counts = all_reduce_sums(sums, counts, process_group)
+    return reduce_means(sums, counts)
+
+
+@torch.no_grad()
 def evaluate(model, directory, num_workers=4, max_count=sys.maxsize, process_group=None):
     """Same signature and return value as the reference's evaluate()
     (src/evaluate.py:171-184): (AUC, MRR, nDCG@5, nDCG@10) of the split in
@@ -127,7 +152,6 @@ def evaluate(model, directory, num_workers=4, max_count=sys.maxsize, process_gro
     for compatibility (there is no process pool). With a torch.distributed
     `process_group`, each rank scores the impressions of its users
     (distributed.user_rank: user_id % world) and the metric sums are all-reduced."""
-    import os
     corpus = read_news_parsed(os.path.join(directory, "news_parsed.tsv"))
     imps = load_behaviors(os.path.join(directory, "behaviors.tsv"))
     return evaluate_split(model, corpus, imps, max_count, process_group)
@@ -135,21 +159,7 @@ def evaluate(model, directory, num_workers=4, max_count=sys.maxsize, process_gro
 
 @torch.no_grad()
 def evaluate_split(model, corpus, impressions, max_count=sys.maxsize, process_group=None):
-    n = len(impressions) if max_count > len(impressions) else max(0, max_count - 1)
-    imps = impressions[:n]
+    imps = cut_impressions(impressions, max_count)
     if process_group is not None:
-        from .distributed import shard_impressions
-        import torch.distributed as dist
         imps = shard_impressions(imps, dist.get_rank(process_group), dist.get_world_size(process_group))
-    plan = EvalPlan(corpus, imps, num_clicked=model.config.num_clicked_news_a_user)
-    if plan.n_impressions:
-        _, metrics = score_plan(model, plan)
-        sums, counts = nan_sums(metrics)
-    else:
-        dev = model.news_encoder.word_embedding.weight.device
-        sums = torch.zeros(4, dtype=torch.float64, device=dev)
-        counts = torch.zeros(4, dtype=torch.float64, device=dev)
-    if process_group is not None:
-        from .distributed import all_reduce_sums
-        sums, counts = all_reduce_sums(sums, counts, process_group)
-    return reduce_means(sums, counts)
+    return evaluate_plan(model, EvalPlan(corpus, imps, num_clicked=model.config.num_clicked_news_a_user), process_group)

@@ -35,17 +35,23 @@ the models are averaged on a schedule that is a function of the step alone
 docstring; DESIGN §Federated fit).
 """
 import csv
+import ctypes
 import os
 import time
 from dataclasses import dataclass, field
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from . import _native as N
 from . import checkpoint as CK
 from . import train as TR
-from .data import NUM_CLICKED, load_behaviors
+from . import train_hip
+from .config import NRMSConfig
+from .data import NUM_CLICKED, BehaviorsTable, load_behaviors, read_news_parsed, write_behaviors_parsed
+from .distributed import shard_impressions, user_rank
+from .evaluate import EvalPlan, cut_impressions, evaluate_plan
 from .splits import index_split
 
 
@@ -89,6 +95,15 @@ class _TitleRowSet:
                                   torch.empty(B, self.N, self.L, dtype=torch.int64, device=self.device))
         self._gather(idx, B, out, *key)
         return out
+
+    def _host_gather(self, rows):
+        """(cand [B, C, L], clicked [B, N, L]) int64 CPU tensors of the title
+        rows int64 [B, C + N]; -1 marks a title the device kernel writes as
+        zeros."""
+        g = self.titles_host[np.where(rows >= 0, rows, 0)]
+        g[rows < 0] = 0
+        return (torch.from_numpy(np.ascontiguousarray(g[:, :self.C])),
+                torch.from_numpy(np.ascontiguousarray(g[:, self.C:])))
 
 
 class TrainSet(_TitleRowSet):
@@ -147,13 +162,10 @@ class TrainSet(_TitleRowSet):
         indexing of the host copies; an index outside [0, S) gives all-zero
         titles for that sample, as the device kernel writes them."""
         idx = np.asarray(torch.as_tensor(sample_idx).cpu(), dtype=np.int64).reshape(-1)
-        S = len(self)
-        ok = (idx >= 0) & (idx < S)
-        r = self.rows_host[np.where(ok, idx, 0)].astype(np.int64)
-        r[~ok] = self.titles_host.shape[0] - 1
-        g = self.titles_host[r]
-        return (torch.from_numpy(np.ascontiguousarray(g[:, :self.C])),
-                torch.from_numpy(np.ascontiguousarray(g[:, self.C:])))
+        ok = (idx >= 0) & (idx < len(self))
+        rows = self.rows_host[np.where(ok, idx, 0)].astype(np.int64)
+        rows[~ok] = -1
+        return self._host_gather(rows)
 
     def _gather(self, idx, B, out):
         N.call("nrms_train_batch_gather", N.ptr(self.titles), self.titles.shape[0], self.L, N.ptr(self.rows),
@@ -165,24 +177,22 @@ MAX_SAMPLED_NEGATIVES = 15          # the sampler keeps 16 hash slots per sample
 _U64 = (1 << 64) - 1
 
 
+def _mix64(x):
+    """The splitmix64 finaliser (stream.mix) on a uint64 array, wrapping."""
+    z = x + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
 def mix64(x):
-    """The splitmix64 finaliser (stream.mix) on a Python int, mod 2^64."""
-    z = (int(x) + 0x9E3779B97F4A7C15) & _U64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _U64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _U64
-    return z ^ (z >> 31)
+    """_mix64 of one Python int, mod 2^64."""
+    return int(_mix64(np.array([int(x) & _U64], dtype=np.uint64))[0])
 
 
 def sampler_base(seed, epoch):
     """mix(mix(uint64(seed)) + uint64(epoch)): the key of one epoch's draws."""
     return mix64((mix64(int(seed) & _U64) + (int(epoch) & _U64)) & _U64)
-
-
-def _mix64_np(x):
-    z = x + np.uint64(0x9E3779B97F4A7C15)
-    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return z ^ (z >> np.uint64(31))
 
 
 def draw_positions(seed, epoch, s, n, k):
@@ -207,7 +217,7 @@ def draw_positions(seed, epoch, s, n, k):
     key = np.uint64(sampler_base(seed, epoch)) + np.uint64(16) * su
     chosen = np.zeros((B, k), dtype=np.uint64)            # columns [0, j): ascending
     for j in range(k):
-        h = _mix64_np(key + np.uint64(j))
+        h = _mix64(key + np.uint64(j))
         r = ((h >> np.uint64(32)) * (nu - np.uint64(j))) >> np.uint64(32)
         for c in range(j):
             r = r + (r >= chosen[:, c]).astype(np.uint64)
@@ -249,7 +259,6 @@ class ImpressionSet(_TitleRowSet):
     _TABLES = ("titles", "pos_row", "pos_imp", "neg_off", "neg_rows", "imp_hist", "hist_rows")
 
     def __init__(self, behaviors_path, corpus, k=None, num_clicked=NUM_CLICKED, device="cpu"):
-        from .config import NRMSConfig
         K = int(NRMSConfig.negative_sampling_ratio if k is None else k)
         if not 0 <= K <= MAX_SAMPLED_NEGATIVES:
             raise ValueError(f"K = {K} outside 0..{MAX_SAMPLED_NEGATIVES}")
@@ -288,7 +297,6 @@ class ImpressionSet(_TitleRowSet):
     @property
     def users(self):
         """Each sample's user: its impression's."""
-        from .data import BehaviorsTable
         u = self._imps.users() if isinstance(self._imps, BehaviorsTable) else [im.user for im in self._imps]
         return [u[i] for i in self.pos_imp_host.tolist()]
 
@@ -353,23 +361,14 @@ class ImpressionSet(_TitleRowSet):
     def host_batch(self, sample_idx, seed=None, epoch=None):
         """(cand [B, C, L], clicked [B, N, L]) int64 CPU tensors: the numpy
         mirror of nrms_train_batch_sample_gather, its zeros included."""
-        seed, epoch = self._key(seed, epoch)
-        rows = self._rows(sample_idx, seed, epoch)
-        g = self.titles_host[np.where(rows >= 0, rows, 0)]
-        g[rows < 0] = 0
-        return (torch.from_numpy(np.ascontiguousarray(g[:, :self.C])),
-                torch.from_numpy(np.ascontiguousarray(g[:, self.C:])))
+        return self._host_gather(self._rows(sample_idx, *self._key(seed, epoch)))
 
     def batch(self, sample_idx, seed=None, epoch=None):
-        """(cand [B, C, L], clicked [B, N, L]) int64 on the set's device. On a
-        GPU: one nrms_train_batch_sample_gather launch (draw + gather) into two
-        buffers this set owns (one pair per batch size; the next call with the
-        same B overwrites them), nothing allocated, no host synchronisation
-        when sample_idx is already an int64 tensor on the device."""
+        """_TitleRowSet.batch with this set's (seed, epoch), or begin_epoch's: on
+        a GPU one nrms_train_batch_sample_gather launch (draw + gather)."""
         return super().batch(sample_idx, *self._key(seed, epoch))
 
     def _gather(self, idx, B, out, seed, epoch):
-        import ctypes
         N.call("nrms_train_batch_sample_gather", N.ptr(self.titles), self.titles.shape[0], self.L,
                N.ptr(self.pos_row), N.ptr(self.pos_imp), self.pos_row.shape[0], N.ptr(self.neg_off),
                self.imp_hist.shape[0], N.ptr(self.neg_rows), self.neg_rows.shape[0], N.ptr(self.imp_hist),
@@ -387,7 +386,6 @@ class ImpressionSet(_TitleRowSet):
         """Write the epoch's samples as a behaviors_parsed.tsv
         (data.write_behaviors_parsed): what TrainSet and the reference's
         BaseDataset read."""
-        from .data import write_behaviors_parsed
         rows = self.materialize(seed, epoch)
         pad = self.titles_host.shape[0] - 1
         ids = self._ids
@@ -447,7 +445,6 @@ def sample_owners(train_set, world):
     """int64 [S]: the client that owns each sample of `train_set`, its user's
     distributed.user_rank. ValueError when the set carries no users (a
     behaviors_parsed.tsv without the `user` column)."""
-    from .distributed import user_rank
     users = train_set.users
     if users is None:
         raise ValueError("a federated fit shards the samples by user: behaviors_parsed.tsv has no `user` column")
@@ -456,16 +453,28 @@ def sample_owners(train_set, world):
                        dtype=np.int64, count=len(users))
 
 
+def _client(train_set, seed=0, rank=0, world=None):
+    """What client `rank` of `world` trains on: (rank, world, its samples
+    int64 [S_r] ascending, [S_0, .., S_{world-1}], client_seed(seed, rank),
+    the set's sample count); every rank computes all of it from the users it
+    loaded, no collective. world None: the one client of a plain fit (no
+    users needed; samples and sizes None)."""
+    if world is None:
+        return 0, 1, None, None, client_seed(seed, 0), len(train_set)
+    owners = sample_owners(train_set, world)
+    return (rank, world, np.flatnonzero(owners == rank).astype(np.int64),
+            np.bincount(owners, minlength=world).tolist(), client_seed(seed, rank), len(owners))
+
+
 def client_shard(train_set, rank, world):
     """int64 [S_r]: the samples of `train_set`, ascending, that client `rank`
     of `world` owns."""
-    return np.flatnonzero(sample_owners(train_set, world) == rank).astype(np.int64)
+    return _client(train_set, 0, rank, world)[2]
 
 
 def shard_sizes(train_set, world):
-    """[S_0, .., S_{world-1}]: every client's sample count (each rank computes
-    all of them from the users it loaded; no collective)."""
-    return np.bincount(sample_owners(train_set, world), minlength=world).tolist()
+    """[S_0, .., S_{world-1}]: every client's sample count."""
+    return _client(train_set, 0, 0, world)[3]
 
 
 def federated_total_steps(num_epochs, S_total, world, batch_size):
@@ -527,43 +536,146 @@ class FitResult:
 
 class _DirValidator:
     """evaluate(model, val_dir, max_count=200000)'s AUC (src/train.py:248-250)
-    with the split read and indexed once (EvalPlan), scored each time.
+    with the split read and indexed once (EvalPlan), scored each time
+    (evaluate.evaluate_plan, where evaluate() ends too).
 
     sharded (a federated fit; `group` its process group, None: the default
-    one): max_count cuts the global impression list first, this rank scores
-    the impressions of the users it owns (distributed.shard_impressions) and
-    the metric sums are all-reduced, so every rank returns the same AUC from
-    the same reduced buffer."""
+    one): max_count cuts the global impression list first, the plan holds the
+    impressions of the users this rank owns (distributed.shard_impressions)
+    and evaluate_plan all-reduces the metric sums, so every rank returns the
+    same AUC from the same reduced buffer."""
 
     def __init__(self, directory, num_clicked, group=None, sharded=False, max_count=200000):
         self.directory, self.num_clicked, self.plan = directory, num_clicked, None
         self.group, self.sharded, self.max_count = group, sharded, max_count
 
     def __call__(self, model):
-        from .data import load_behaviors, read_news_parsed
-        from .evaluate import EvalPlan, nan_sums, reduce_means, score_plan
         if self.plan is None:
             corpus = read_news_parsed(os.path.join(self.directory, "news_parsed.tsv"))
-            imps = load_behaviors(os.path.join(self.directory, "behaviors.tsv"))
+            imps = cut_impressions(load_behaviors(os.path.join(self.directory, "behaviors.tsv")), self.max_count)
             if self.sharded:
-                import torch.distributed as dist
+                self.group = dist.group.WORLD if self.group is None else self.group
+                imps = shard_impressions(imps, dist.get_rank(self.group), dist.get_world_size(self.group))
+            self.plan = EvalPlan(corpus, imps, num_clicked=self.num_clicked)
+        return evaluate_plan(model, self.plan, self.group if self.sharded else None)[0]
 
-                from .distributed import shard_impressions
-                n = len(imps) if self.max_count > len(imps) else max(0, self.max_count - 1)   # EvalPlan's cut
-                imps = shard_impressions(imps[:n], dist.get_rank(self.group), dist.get_world_size(self.group))
-                self.plan = EvalPlan(corpus, imps, num_clicked=self.num_clicked)
-            else:
-                self.plan = EvalPlan(corpus, imps, max_count=self.max_count, num_clicked=self.num_clicked)
-        if not self.sharded:
-            _, metrics = score_plan(model, self.plan)
-            return reduce_means(*nan_sums(metrics))[0]
-        from .distributed import all_reduce_sums
-        if self.plan.n_impressions:
-            sums, counts = nan_sums(score_plan(model, self.plan)[1])
+
+def _resume(checkpoint_dir, model, optimizer, early, fed, rank, say, log):
+    """Continue from the latest checkpoint of `checkpoint_dir`, if it has one:
+    (its step, its path), else (0, None). Rank r > 0 takes its own optimizer
+    file, or logs that it has none; EarlyStopping is primed with the
+    checkpoint's value (src/train.py:148)."""
+    os.makedirs(checkpoint_dir, exist_ok=True)
+    if fed is not None and fed.world > 1:
+        fed.dist.barrier(group=fed.group)             # files an earlier call of another rank still writes
+    path = CK.latest_checkpoint(checkpoint_dir)
+    if path is None:
+        return 0, None
+    say(f"Load saved parameters in {path}")
+    if rank == 0:
+        start, esv = CK.resume(path, model, optimizer)
+    else:
+        start, esv, own = CK.resume_rank(path, rank, model, optimizer)
+        if not own:
+            log(f"rank {rank}: no {os.path.basename(CK.rank_path(path, rank))}, taking rank 0's optimizer state")
+    early(esv)
+    return start, path
+
+
+class _LossRing:
+    """Every step's loss without a read-back per step: a device route writes
+    step t's loss to slot(t) = t % size of the device log `log` (flushing
+    first when every slot is marked) and marks the slot; flush() appends the
+    marked slots to the host list `losses` with one copy. The host_batches
+    route appends to `losses` itself (size 0)."""
+
+    def __init__(self, size, device):
+        self.losses = []
+        self.log = torch.zeros(size, dtype=torch.float32, device=device)
+        self.pending = []               # slots of log not yet copied back, in step order
+
+    def slot(self, t):
+        if len(self.pending) == self.log.numel():
+            self.flush()
+        return t % self.log.numel()
+
+    def mark(self, slot):
+        self.pending.append(slot)
+
+    def flush(self):
+        if self.pending:
+            host = self.log.cpu()
+            self.losses.extend(host[self.pending].tolist())
+            self.pending.clear()
+
+
+# The three routes of a step. Each returns step(t, idx): global step t on the
+# samples idx of train_set, its loss recorded in `ring`.
+def _hip_step(model, optimizer, train_set, ring, cseed):
+    """Device batch, HIP forward, loss + gradient in one launch into the ring."""
+    def step(t, idx):
+        slot = ring.slot(t)
+        cand, clk = train_set.batch(idx)
+        logits = train_hip.forward_hip(model, cand, clk, seed=dropout_seed(cseed, t))
+        _, dlogits = xent_class0(logits.detach(), loss_out=ring.log[slot:slot + 1])
+        TR.backward_step(optimizer, logits, dlogits)
+        ring.mark(slot)
+    return step
+
+
+def _aten_step(model, optimizer, train_set, ring, cseed):
+    """train.train_step (the CPU, or a GPU model without hip_train; torch's dropout)."""
+    def step(t, idx):
+        slot = ring.slot(t)
+        ring.log[slot].copy_(TR.train_step(model, optimizer, *train_set.batch(idx)))
+        ring.mark(slot)
+    return step
+
+
+def _host_batches_step(model, optimizer, train_set, ring, cseed):
+    """_hip_step's baseline: host-assembled batch, torch's loss kernels, loss.item()."""
+    dev = next(model.parameters()).device
+
+    def step(t, idx):
+        cand, clk = train_set.host_batch(idx)
+        logits = train_hip.forward_hip(model, cand.to(dev), clk.to(dev), seed=dropout_seed(cseed, t))
+        loss = TR.loss_fn(logits)
+        TR.backward_step(optimizer, loss)
+        ring.losses.append(loss.item())
+    return step
+
+
+def _epoch_samples(train_set, cseed, seed, e, S, owned, device):
+    """Epoch e's samples in training order: epoch_order(cseed, e, S) on
+    `device` (None: the host), through `owned` for a federated client. An
+    ImpressionSet is told the (seed, e) it draws with."""
+    order = epoch_order(cseed, e, S)
+    if hasattr(train_set, "begin_epoch"):
+        train_set.begin_epoch(seed, e)
+    if device is not None:
+        order = order.to(device)
+    return order if owned is None else owned[order]           # local -> global sample, on the device
+
+
+def _validated(t, model, validate, early, res, checkpoint_dir, rank, say):
+    """Validation after step t, early stopping (True: stop), and the
+    checkpoint on improvement."""
+    model.eval()
+    auc = float(validate(model))
+    model.train()
+    res.aucs.append((t, auc))
+    say(f"batches {t}, validation AUC: {auc:.4f}")
+    stop, better = early(-auc)
+    if stop:
+        say("Early stop.")
+        res.early_stopped = True
+    elif better and checkpoint_dir is not None:
+        res.checkpoint = os.path.join(checkpoint_dir, f"ckpt-{t}.pth")
+        if rank == 0:
+            CK.save(res.checkpoint, model, res.optimizer, t, -auc)
         else:
-            dev = next(model.parameters()).device
-            sums, counts = (torch.zeros(4, dtype=torch.float64, device=dev) for _ in range(2))
-        return reduce_means(*all_reduce_sums(sums, counts, self.group))[0]
+            CK.save_rank(res.checkpoint, rank, res.optimizer, t)
+    return stop
 
 
 def fit(model, train_set, val=None, *, checkpoint_dir=None, seed=0, steps=None, batch_size=None,
@@ -598,20 +710,15 @@ def fit(model, train_set, val=None, *, checkpoint_dir=None, seed=0, steps=None, 
     cfg = model.config
     dev = next(model.parameters()).device
     B = int(batch_size if batch_size is not None else cfg.batch_size)
-    S = len(train_set)
-    rank, world, owned, cseed = 0, 1, None, seed
-    if fed is not None:
-        if host_batches:
-            raise ValueError("host_batches is the single-client baseline route: not with fed")
-        rank, world = fed.dist.get_rank(fed.group), fed.world
-        owners = sample_owners(train_set, world)                   # raises without users
-        sizes = np.bincount(owners, minlength=world).tolist()
-        owned = np.flatnonzero(owners == rank).astype(np.int64)
-        for r, n in enumerate(sizes):                              # every rank raises, naming the short one
-            if B > 0 and n < B:
-                raise ValueError(f"rank {r}: its shard of {n} samples (of {S}, world {world}) is smaller than "
-                                 f"the batch size {B}")
-        S_total, S, cseed = S, int(owned.size), client_seed(seed, rank)
+    if fed is not None and host_batches:
+        raise ValueError("host_batches is the single-client baseline route: not with fed")
+    rank, world, owned, sizes, cseed, S_total = (                                      # raises without users
+        _client(train_set, seed) if fed is None else _client(train_set, seed, fed.dist.get_rank(fed.group), fed.world))
+    S = S_total if fed is None else int(owned.size)
+    for r, n in enumerate(sizes or ()):                       # every rank raises, naming the short one
+        if B > 0 and n < B:
+            raise ValueError(f"rank {r}: its shard of {n} samples (of {S_total}, world {world}) is smaller than "
+                             f"the batch size {B}")
     if B <= 0 or S // B == 0:
         raise ValueError(f"batch size {B} leaves no full batch of {S} samples (drop_last)")
     if train_set.min_id < 0 or train_set.max_id >= cfg.num_words:
@@ -621,53 +728,28 @@ def fit(model, train_set, val=None, *, checkpoint_dir=None, seed=0, steps=None, 
         raise ValueError("host_batches is the baseline of the HIP route (a GPU model with hip_train)")
     if dev.type == "cuda" and not host_batches and train_set.device != dev:
         raise ValueError(f"train set on {train_set.device}, model on {dev}")
-    if hip:
-        from . import train_hip
+
     optimizer = TR.make_optimizer(model)
     early = EarlyStopping()
-    res = FitResult(optimizer=optimizer)
+    res = FitResult(optimizer=optimizer, shard_sizes=sizes)
     say = log if rank == 0 else (lambda *_: None)
     if checkpoint_dir is not None:
-        os.makedirs(checkpoint_dir, exist_ok=True)
-        if fed is not None and world > 1:
-            fed.dist.barrier(group=fed.group)             # files an earlier call of another rank still writes
-        path = CK.latest_checkpoint(checkpoint_dir)
-        if path is not None:
-            say(f"Load saved parameters in {path}")
-            if rank == 0:
-                res.start_step, esv = CK.resume(path, model, optimizer)
-            else:
-                res.start_step, esv, own = CK.resume_rank(path, rank, model, optimizer)
-                if not own:
-                    log(f"rank {rank}: no {os.path.basename(CK.rank_path(path, rank))}, "
-                        f"taking rank 0's optimizer state")
-            early(esv)                                    # src/train.py:148
-            res.checkpoint = path
+        res.start_step, res.checkpoint = _resume(checkpoint_dir, model, optimizer, early, fed, rank, say, log)
     if validate is None and val is not None:
         validate = _DirValidator(val, cfg.num_clicked_news_a_user, group=fed.group if fed is not None else None,
                                  sharded=fed is not None)
     if steps is None:
-        total = cfg.num_epochs * S // B if fed is None else federated_total_steps(cfg.num_epochs, S_total, world, B)
-        steps = max(0, total - res.start_step)
+        steps = max(0, federated_total_steps(cfg.num_epochs, S_total, world, B) - res.start_step)
     if fed is not None:
         fed.broadcast(0)                                  # one model, whatever each rank was seeded with
-        res.shard_sizes = sizes
         owned = torch.from_numpy(owned).to(dev)
     model.train()
-
     show, every = int(cfg.num_batches_show_loss), int(cfg.num_batches_validate)
-    losses = []
-    loss_log = torch.zeros(max(show, 1), dtype=torch.float32, device=dev) if not host_batches else None
-    pending = []                    # slots of loss_log not yet copied back, in step order
-
-    def flush():
-        if pending:
-            host = loss_log.cpu()
-            losses.extend(host[pending].tolist())
-            pending.clear()
+    ring = _LossRing(0 if host_batches else max(show, 1), dev)
+    step = (_host_batches_step if host_batches else _hip_step if hip else _aten_step)(
+        model, optimizer, train_set, ring, cseed)
 
     epoch, order = None, None
-    begin_epoch = getattr(train_set, "begin_epoch", None)   # an ImpressionSet draws per (seed, epoch)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
@@ -676,67 +758,25 @@ def fit(model, train_set, val=None, *, checkpoint_dir=None, seed=0, steps=None, 
     for t in range(res.start_step + 1, last + 1):
         e, a, b = batch_of_step(t, S, B)
         if e != epoch:
-            epoch, order = e, epoch_order(cseed, e, S)
-            if begin_epoch is not None:
-                begin_epoch(seed, e)
-            if dev.type == "cuda" and not host_batches:
-                order = order.to(dev)
-            if owned is not None:
-                order = owned[order]                      # local -> global sample, on the device
-        if host_batches:
-            cand, clk = train_set.host_batch(order[a:b])
-            logits = train_hip.forward_hip(model, cand.to(dev), clk.to(dev), seed=dropout_seed(cseed, t))
-            loss = TR.loss_fn(logits)
-            optimizer.zero_grad()
-            loss.backward()
-            optimizer.step()
-            losses.append(loss.item())
-        else:
-            if len(pending) == loss_log.numel():
-                flush()
-            slot = t % loss_log.numel()
-            cand, clk = train_set.batch(order[a:b])
-            if hip:
-                logits = train_hip.forward_hip(model, cand, clk, seed=dropout_seed(cseed, t))
-                _, dlogits = xent_class0(logits.detach(), loss_out=loss_log[slot:slot + 1])
-                optimizer.zero_grad()
-                logits.backward(dlogits)
-                optimizer.step()
-            else:
-                loss_log[slot].copy_(TR.train_step(model, optimizer, cand, clk))
-            pending.append(slot)
+            epoch, order = e, _epoch_samples(train_set, cseed, seed, e, S, owned, None if host_batches else dev)
+        step(t, order[a:b])
         if fed is not None and sync_due(t, fed.every, every if validate is not None else 0, last):
             fed.sync()
             res.syncs += 1
         if show > 0 and t % show == 0:
-            flush()
-            say(f"batches {t}, current loss {losses[-1]:.4f}, average loss: {np.mean(losses):.4f}, "
-                f"latest average loss: {np.mean(losses[-256:]):.4f}")        # src/train.py:241-244
+            ring.flush()
+            say(f"batches {t}, current loss {ring.losses[-1]:.4f}, average loss: {np.mean(ring.losses):.4f}, "
+                f"latest average loss: {np.mean(ring.losses[-256:]):.4f}")        # src/train.py:241-244
         if validate is not None and every > 0 and t % every == 0:
-            flush()
-            model.eval()
-            auc = float(validate(model))
-            model.train()
-            res.aucs.append((t, auc))
-            say(f"batches {t}, validation AUC: {auc:.4f}")
-            stop, better = early(-auc)
-            if stop:
-                say("Early stop.")
-                res.early_stopped = True
+            ring.flush()
+            if _validated(t, model, validate, early, res, checkpoint_dir, rank, say):
                 break
-            if better and checkpoint_dir is not None:
-                res.checkpoint = os.path.join(checkpoint_dir, f"ckpt-{t}.pth")
-                if rank == 0:
-                    CK.save(res.checkpoint, model, optimizer, t, -auc)
-                else:
-                    CK.save_rank(res.checkpoint, rank, optimizer, t)
-    flush()
+    ring.flush()
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     res.seconds = time.perf_counter() - t0
-    res.steps = len(losses)
-    res.step = t
-    res.losses = torch.tensor(losses, dtype=torch.float32)
+    res.steps, res.step = len(ring.losses), t
+    res.losses = torch.tensor(ring.losses, dtype=torch.float32)
     res.best_loss = early.best_loss
     res.best_auc = None if not np.isfinite(early.best_loss) else float(-early.best_loss)
     return res

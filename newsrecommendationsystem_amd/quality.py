@@ -21,6 +21,7 @@ exchange is the same arithmetic); tests/test_gpu_multiprocess.py runs the HIP
 clients as two processes over a real process group.
 """
 import copy
+import os
 import tempfile
 import time
 
@@ -31,7 +32,9 @@ from . import data as Dt
 from . import train as TR
 from .config import NRMSConfig
 from .evaluate import EvalPlan, evaluate, score_plan
+from .fit import ImpressionSet, TrainSet, fit
 from .nrms import NRMS
+from .train_hip import hip_dropout_masks
 
 
 def make_config(V, lr=2e-3, dropout=0.0):
@@ -78,14 +81,28 @@ def teacher_batches(teacher, titles, seed, n_batches, B, C=3, N=50):
     return out
 
 
-def train_clients(init, client_batches, every, device):
+def _fedavg_(models):
+    """Replace every client's parameters by the clients' mean (train.FedAvg's
+    exchange: sum over clients / count)."""
+    with torch.no_grad():
+        for ps in zip(*[list(m.parameters()) for m in models]):
+            acc = ps[0].detach().clone()
+            for p in ps[1:]:
+                acc += p.detach()
+            acc /= len(ps)
+            for p in ps:
+                p.copy_(acc)
+
+
+def _train_clients(init, client_batches, every, device, make_optimizer, step):
     """FedAvg over len(client_batches) clients, each its own copy of `init`
-    (on `device`) and its own optimizer (train.make_optimizer: HipAdam on a
-    GPU, torch Adam on the CPU); after every `every` local steps the
-    parameters of all clients are replaced by their mean. Returns (model,
-    seconds spent in the local steps, steps taken per client)."""
+    (on `device`) and its own optimizer make_optimizer(model); a client's
+    local step k (from 0) is step(model, optimizer, k, cand, clk) on its k-th
+    batch, and after every `every` local steps the parameters of all clients
+    are replaced by their mean. Returns (model, seconds spent in the local
+    steps, steps taken per client)."""
     models = [copy.deepcopy(init).to(device) for _ in client_batches]
-    opts = [TR.make_optimizer(m) for m in models]
+    opts = [make_optimizer(m) for m in models]
     steps = len(client_batches[0])
     t_steps = 0.0
     for k in range(steps):
@@ -94,20 +111,40 @@ def train_clients(init, client_batches, every, device):
             if device.type == "cuda":
                 torch.cuda.synchronize(device)
             t0 = time.perf_counter()
-            TR.train_step(m, opt, cand.to(device), clk.to(device))
+            step(m, opt, k, cand.to(device), clk.to(device))
             if device.type == "cuda":
                 torch.cuda.synchronize(device)
             t_steps += time.perf_counter() - t0
         if every > 0 and (k + 1) % every == 0:
-            with torch.no_grad():
-                for ps in zip(*[list(m.parameters()) for m in models]):
-                    acc = ps[0].detach().clone()
-                    for p in ps[1:]:
-                        acc += p.detach()
-                    acc /= len(ps)
-                    for p in ps:
-                        p.copy_(acc)
+            _fedavg_(models)
     return models[0], t_steps, steps
+
+
+def train_clients(init, client_batches, every, device):
+    """_train_clients on the product path: train.make_optimizer (HipAdam on a
+    GPU, torch Adam on the CPU) and train.train_step."""
+    return _train_clients(init, client_batches, every, device, TR.make_optimizer,
+                          lambda m, opt, k, cand, clk: TR.train_step(m, opt, cand, clk))
+
+
+def train_clients_reference(init, client_batches, every, device):
+    """_train_clients on the reference's op sequence (train.forward_autograd,
+    ATen autograd, CrossEntropy vs class 0) with torch.optim.Adam. With
+    dropout p > 0 the step takes the HIP step's dropout sample: its masks come
+    from the HIP generator with the same per-call seed the HIP student uses
+    (1, 2, ... per client, NRMS.forward_ids) and enter as forward_autograd's
+    explicit multiplicative masks."""
+    p = float(init.config.dropout_probability)
+
+    def step(m, opt, k, cand, clk):
+        m.train()
+        masks = None
+        if p > 0:
+            B, C, L = cand.shape
+            masks = hip_dropout_masks(B * (C + clk.shape[1]) * L, 300, p, k + 1, device)
+        TR.backward_step(opt, TR.loss_fn(TR.forward_autograd(m, cand, clk, training=False, masks=masks)))
+    return _train_clients(init, client_batches, every, device,
+                          lambda m: torch.optim.Adam(m.parameters(), lr=m.config.learning_rate), step)
 
 
 def setup(directory, V=5000, n_news=3000, n_users=800, n_impressions=1500, seed=0, lr=2e-3):
@@ -119,6 +156,19 @@ def setup(directory, V=5000, n_news=3000, n_users=800, n_impressions=1500, seed=
                                       n_impressions=n_impressions, V=V, teacher=teacher_logits_fn(teacher))
     student = model_from_seed(cfg, 2000 + seed)
     return cfg, teacher, corpus, np.asarray(corpus.titles, dtype=np.int64), student
+
+
+def _cpu_state(model):
+    return {k: v.detach().cpu() for k, v in model.state_dict().items()}
+
+
+def _param_diff(sd, ref_sd):
+    # the largest normwise relative difference of a parameter. W_K's bias has
+    # an analytically zero gradient (the normalisation divides a key bias out),
+    # so Adam turns either path's rounding noise into +-lr steps there: it is
+    # left out of the comparison
+    return max(float((sd[k] - ref_sd[k]).norm() / ref_sd[k].norm().clamp_min(1e-30))
+               for k in ref_sd if not k.endswith("W_K.bias"))
 
 
 def auc_of(model_state, cfg, directory):
@@ -136,7 +186,7 @@ def run(steps=32, every=4, world=2, B=16, C=3, seed=0, cpu=True):
         client_batches = [teacher_batches(teacher, titles, 100 + 17 * r + seed, steps, B, C) for r in range(world)]
         init_auc = auc_of(student.state_dict(), cfg, d)
         hip, t_hip, n = train_clients(student, client_batches, every, torch.device("cuda"))
-        hip_sd = {k: v.detach().cpu() for k, v in hip.state_dict().items()}
+        hip_sd = _cpu_state(hip)
         auc_hip = auc_of(hip_sd, cfg, d)
         out = {"workload": (f"planted teacher: {world} FedAvg clients x {steps} local steps (batch {B}, "
                             f"1+K={C}, 50 clicked, V={cfg.num_words}, lr {cfg.learning_rate}, dropout 0, "
@@ -146,13 +196,9 @@ def run(steps=32, every=4, world=2, B=16, C=3, seed=0, cpu=True):
                "hip_train_steps_per_s": round(world * n / t_hip, 2)}
         if cpu:
             cpu_m, t_cpu, _ = train_clients(student, client_batches, every, torch.device("cpu"))
-            cpu_sd = {k: v.detach().cpu() for k, v in cpu_m.state_dict().items()}
+            cpu_sd = _cpu_state(cpu_m)
             auc_cpu = auc_of(cpu_sd, cfg, d)
-            # (W_K's bias has an analytically zero gradient -- the normalisation
-            # divides a key bias out -- so Adam turns either path's rounding
-            # noise into +-lr steps there; it is left out of the comparison)
-            diff = max(float((hip_sd[k] - cpu_sd[k]).norm() / cpu_sd[k].norm().clamp_min(1e-30))
-                       for k in cpu_sd if not k.endswith("W_K.bias"))
+            diff = _param_diff(hip_sd, cpu_sd)
             out.update({"auc_cpu": auc_cpu[0], "abs_diff_auc": abs(auc_hip[0] - auc_cpu[0]),
                         "tolerance": 0.002, "cpu_train_steps_per_s": round(world * n / t_cpu, 2),
                         "max_normwise_param_diff_hip_vs_cpu_excl_WK_bias": diff,
@@ -181,56 +227,6 @@ def teacher_batches_device(teacher, titles, seed, n_batches, B, C=3, N=50):
         cand = torch.gather(cand, 1, order[:, :, None].expand(-1, -1, L))
         out.append((cand.contiguous(), clk.contiguous()))
     return out
-
-
-def _fedavg_(models):
-    """Replace every client's parameters by the clients' mean (train.FedAvg's
-    exchange: sum over clients / count)."""
-    with torch.no_grad():
-        for ps in zip(*[list(m.parameters()) for m in models]):
-            acc = ps[0].detach().clone()
-            for p in ps[1:]:
-                acc += p.detach()
-            acc /= len(ps)
-            for p in ps:
-                p.copy_(acc)
-
-
-def train_clients_reference(init, client_batches, every, device):
-    """The same FedAvg schedule on the reference's op sequence (train.py:
-    forward_autograd, ATen autograd, CrossEntropy vs class 0) with
-    torch.optim.Adam, on `device`. With dropout p > 0 the step takes the HIP
-    step's dropout sample: its masks come from the HIP generator with the same
-    per-call seed the HIP student uses (1, 2, ... per client, NRMS.forward_ids)
-    and enter as explicit multiplicative masks (train.forward_autograd_masked)."""
-    models = [copy.deepcopy(init).to(device) for _ in client_batches]
-    opts = [torch.optim.Adam(m.parameters(), lr=m.config.learning_rate) for m in models]
-    p = float(init.config.dropout_probability)
-    steps = len(client_batches[0])
-    t_steps = 0.0
-    for k in range(steps):
-        for m, opt, batches in zip(models, opts, client_batches):
-            cand, clk = (t.to(device) for t in batches[k])
-            if device.type == "cuda":
-                torch.cuda.synchronize(device)
-            t0 = time.perf_counter()
-            m.train()
-            if p > 0:
-                B, C, L = cand.shape
-                masks = TR.hip_dropout_masks(B * (C + clk.shape[1]) * L, 300, p, k + 1, device)
-                logits = TR.forward_autograd_masked(m, cand, clk, masks)
-            else:
-                logits = TR.forward_autograd(m, cand, clk, training=False)
-            loss = TR.loss_fn(logits)
-            opt.zero_grad()
-            loss.backward()
-            opt.step()
-            if device.type == "cuda":
-                torch.cuda.synchronize(device)
-            t_steps += time.perf_counter() - t0
-        if every > 0 and (k + 1) % every == 0:
-            _fedavg_(models)
-    return models[0], t_steps, steps
 
 
 def run_scaled(steps=320, every=10, world=2, B=128, C=3, V=70976, n_news=20000, dropouts=(0.0, 0.2),
@@ -266,14 +262,13 @@ def run_scaled(steps=320, every=10, world=2, B=128, C=3, V=70976, n_news=20000, 
             student = NRMS(cfg, torch.randn(V, 300) * 0.5)
             init_auc = auc_of(student.state_dict(), cfg, d)
             hip, t_hip, n = train_clients(student, client_batches, every, dev)
-            hip_sd = {k: v.detach().cpu() for k, v in hip.state_dict().items()}
+            hip_sd = _cpu_state(hip)
             del hip
             ref, t_ref, _ = train_clients_reference(student, client_batches, every, dev)
-            ref_sd = {k: v.detach().cpu() for k, v in ref.state_dict().items()}
+            ref_sd = _cpu_state(ref)
             del ref
             a_hip, a_ref = auc_of(hip_sd, cfg, d), auc_of(ref_sd, cfg, d)
-            diff = max(float((hip_sd[k] - ref_sd[k]).norm() / ref_sd[k].norm().clamp_min(1e-30))
-                       for k in ref_sd if not k.endswith("W_K.bias"))
+            diff = _param_diff(hip_sd, ref_sd)
             res["runs"].append({
                 "dropout": p, "auc_init": init_auc[0], "auc_hip": a_hip[0], "auc_reference": a_ref[0],
                 "auc_lift_hip": a_hip[0] - init_auc[0], "abs_diff_auc": abs(a_hip[0] - a_ref[0]),
@@ -297,9 +292,6 @@ def resample_vs_static(epochs=6, B=64, V=5000, n_news=3000, n_users=800, n_impre
     ~2,000 steps of six epochs here both routes reached a NaN loss in epoch 5
     with it, so the default is lower. temperature: run_scaled's 0.5. Returns
     the report text: validation AUC after each epoch."""
-    import os
-
-    from .fit import ImpressionSet, TrainSet, fit
     dev = torch.device("cuda", 0)
     cfg = make_config(V, lr, dropout)
     teacher = model_from_seed(cfg, 1000 + seed).to(dev).eval()

@@ -12,10 +12,10 @@ FedAvg exchange: `FedAvg.sync()` averages the 21,955,400 fp32 parameters
 tests check the exchange itself (every rank ends with the exact mean) and the
 single-process step against the CPU restatement's autograd. The loop around
 the step (src/train.py:67-279: batches of a MIND directory, validation, early
-stopping, checkpoints) is fit.py; `python -m newsrecommendationsystem_amd.train
-DIR` runs it, and `DIR --gpus N` runs it federated: one client per rank,
-FedAvg's exchange (two HIP launches around the all-reduce, csrc/fedavg.hip)
-on fit's schedule.
+stopping, checkpoints) is fit.py. The command line `python -m
+newsrecommendationsystem_amd.train` is train_cli.py: `DIR` runs fit, and `DIR
+--gpus N` runs it federated: one client per rank, FedAvg's exchange (two HIP
+launches around the all-reduce, csrc/fedavg.hip) on fit's schedule.
 
 Semantics kept from the reference:
   * dropout p = config.dropout_probability on the embedding output and on the
@@ -25,10 +25,16 @@ Semantics kept from the reference:
     (src/train.py:126,205-206); Adam(lr = config.learning_rate) (:127);
   * nn.Embedding(padding_idx=0): row 0 receives no gradient.
 """
+import ctypes
 import math
 
 import torch
+import torch.distributed as dist
 import torch.nn.functional as F
+
+from . import _native as N
+from .distributed import all_reduce_, broadcast_
+from .train_hip import HipAdam
 
 
 def _mhsa(x, m):
@@ -50,11 +56,19 @@ def _additive(x, m):
     return torch.bmm(w.unsqueeze(1), x).squeeze(1)
 
 
-def news_encode_autograd(ne, ids, training=True):
-    """NewsEncoder.forward (news_encoder.py:27-48) with autograd."""
-    p = ne.config.dropout_probability
-    x = F.dropout(ne.word_embedding(ids), p=p, training=training)
-    h = F.dropout(_mhsa(x, ne.multihead_self_attention), p=p, training=training)
+def news_encode_autograd(ne, ids, training=True, masks=None):
+    """NewsEncoder.forward (news_encoder.py:27-48) with autograd. masks (m1,
+    m2): the two dropouts (news_encoder.py:38-45) are these multiplications
+    instead of torch's draw, m1 on the embedding output, m2 on the MHSA
+    output, each with ids.numel() rows."""
+    if masks is None:
+        p = ne.config.dropout_probability
+        x = F.dropout(ne.word_embedding(ids), p=p, training=training)
+        h = F.dropout(_mhsa(x, ne.multihead_self_attention), p=p, training=training)
+    else:
+        n, L = ids.shape
+        x = ne.word_embedding(ids) * masks[0].view(n, L, -1)
+        h = _mhsa(x, ne.multihead_self_attention) * masks[1].view(n, L, -1)
     return _additive(h, ne.additive_attention)
 
 
@@ -63,11 +77,13 @@ def user_encode_autograd(ue, clicked_vec):
     return _additive(_mhsa(clicked_vec, ue.multihead_self_attention), ue.additive_attention)
 
 
-def forward_autograd(model, cand_ids, clicked_ids, training=True):
+def forward_autograd(model, cand_ids, clicked_ids, training=True, masks=None):
     """NRMS.forward (src/model/NRMS/__init__.py:19-48) with autograd: all
     B*(C+N) titles go through the encoder in one call (the reference encodes the
     55 slots one by one; per-title results and the dropout distribution are the
-    same)."""
+    same). masks (m1, m2): dropout as explicit multiplicative masks over the
+    titles in the HIP step's order [candidates B*C | clicked B*N]
+    (train_hip.hip_dropout_masks), whatever `training` says."""
     ne, ue = model.news_encoder, model.user_encoder
     dev = ne.word_embedding.weight.device
     cand = cand_ids.to(dev)
@@ -75,48 +91,12 @@ def forward_autograd(model, cand_ids, clicked_ids, training=True):
     B, C, L = cand.shape
     n_clicked = clk.shape[1]
     vec = news_encode_autograd(ne, torch.cat([cand.reshape(B * C, L), clk.reshape(B * n_clicked, L)]),
-                               training)
+                               training, masks)
     D = vec.shape[-1]
     cand_vec = vec[:B * C].view(B, C, D)
     clk_vec = vec[B * C:].view(B, n_clicked, D)
     user = user_encode_autograd(ue, clk_vec)
     return torch.bmm(cand_vec, user.unsqueeze(-1)).squeeze(-1)
-
-
-def hip_dropout_masks(n_rows, D, p, seed, device):
-    """The two multiplicative dropout masks ([n_rows, D], 0 or 1/(1-p)) that
-    the HIP training step with dropout seed `seed` applies (train_hip.py:
-    nrms_dropout on the embedding output with seed 2s, on the MHSA output with
-    seed 2s+1), generated by the same kernel on a tensor of ones: fed to
-    forward_autograd_masked they make the reference op sequence take exactly
-    the HIP step's dropout sample."""
-    import ctypes
-    from . import _native as N
-    ones = torch.ones(n_rows * D, device=device)
-    out = []
-    for s in (2 * int(seed), 2 * int(seed) + 1):
-        mk = torch.empty_like(ones)
-        N.call("nrms_dropout", N.ptr(ones), N.ptr(mk), ones.numel(), ctypes.c_float(p), ctypes.c_uint64(s),
-               N.stream_handle(device))
-        out.append(mk.view(n_rows, D))
-    return out
-
-
-def forward_autograd_masked(model, cand_ids, clicked_ids, masks):
-    """forward_autograd with dropout as explicit multiplicative masks (m1 on
-    the embedding output, m2 on the MHSA output, news_encoder.py:38-45), the
-    titles in the HIP step's order [candidates B*C | clicked B*N]."""
-    ne, ue = model.news_encoder, model.user_encoder
-    B, C, L = cand_ids.shape
-    n_clicked = clicked_ids.shape[1]
-    m1, m2 = masks
-    ids = torch.cat([cand_ids.reshape(B * C, L), clicked_ids.reshape(B * n_clicked, L)])
-    x = ne.word_embedding(ids) * m1.view(ids.shape[0], L, -1)
-    h = _mhsa(x, ne.multihead_self_attention) * m2.view(ids.shape[0], L, -1)
-    vec = _additive(h, ne.additive_attention)
-    D = vec.shape[-1]
-    user = user_encode_autograd(ue, vec[B * C:].view(B, n_clicked, D))
-    return torch.bmm(vec[:B * C].view(B, C, D), user.unsqueeze(-1)).squeeze(-1)
 
 
 def loss_fn(logits):
@@ -125,16 +105,21 @@ def loss_fn(logits):
                                                device=logits.device))
 
 
+def backward_step(optimizer, out, grad=None):
+    """zero_grad, out.backward(grad), optimizer.step (src/train.py:230-236):
+    `out` the loss, or the logits with the loss's gradient `grad`."""
+    optimizer.zero_grad()
+    out.backward(grad)
+    optimizer.step()
+
+
 def train_step(model, optimizer, cand_ids, clicked_ids):
     """One iteration of the loop body of src/train.py:202-236. On a GPU the
     forward/backward are the HIP training kernels (model.forward_ids in train
     mode -> train_hip.NRMSTrain); on the CPU, ATen autograd."""
     model.train()
-    logits = model.forward_ids(cand_ids, clicked_ids)
-    loss = loss_fn(logits)
-    optimizer.zero_grad()
-    loss.backward()
-    optimizer.step()
+    loss = loss_fn(model.forward_ids(cand_ids, clicked_ids))
+    backward_step(optimizer, loss)
     return loss.detach()
 
 
@@ -164,7 +149,6 @@ class FedAvg:
     a parameter that is not a contiguous float32 tensor on flat's device."""
 
     def __init__(self, model, every, group=None, native=None):
-        import torch.distributed as dist
         self.dist = dist
         self.group = group
         self.every = int(every)
@@ -182,9 +166,6 @@ class FedAvg:
 
     def _descriptors(self):
         """(host array of nrms_flat_tensor_t, n) for the parameters as they lie now."""
-        import ctypes
-
-        from . import _native as N
         key = tuple(p.data_ptr() for p in self.params)
         if key != self._table_key:
             for p in self.params:
@@ -202,7 +183,6 @@ class FedAvg:
 
     def _pack(self):
         if self.native:
-            from . import _native as N
             tab, n = self._descriptors()
             N.call("nrms_params_pack", tab, n, N.ptr(self.flat), N.stream_handle(self.flat.device))
             return
@@ -214,9 +194,6 @@ class FedAvg:
 
     def _unpack(self, divisor):
         if self.native:
-            import ctypes
-
-            from . import _native as N
             tab, n = self._descriptors()
             N.call("nrms_params_unpack_div", tab, n, N.ptr(self.flat), ctypes.c_float(divisor),
                    N.stream_handle(self.flat.device))
@@ -235,7 +212,6 @@ class FedAvg:
     def sync(self):
         """pack -> all-reduce -> unpack / world: three device operations on
         the native route, 19 + 1 + 1 + 19 on the torch one."""
-        from .distributed import all_reduce_
         self._pack()
         all_reduce_(self.flat, self.group)
         self._unpack(self.world)
@@ -245,7 +221,6 @@ class FedAvg:
         """Every rank takes rank `src`'s parameters (bitwise): pack, broadcast
         of `flat`, unpack with divisor 1. A CUDA `flat` under gloo goes through
         host memory, as distributed.all_reduce_ does."""
-        from .distributed import broadcast_
         self._pack()
         broadcast_(self.flat, src, self.group)
         self._unpack(1 if self.native else None)
@@ -263,7 +238,6 @@ def make_optimizer(model):
     """Adam(lr = config.learning_rate) (src/train.py:127): the HIP update
     (train_hip.HipAdam, same state keys) on a GPU, torch.optim.Adam on CPU."""
     if next(model.parameters()).is_cuda:
-        from .train_hip import HipAdam
         return HipAdam(model.parameters(), lr=model.config.learning_rate)
     return torch.optim.Adam(model.parameters(), lr=model.config.learning_rate)
 
@@ -285,418 +259,6 @@ def synthetic_train_batches(seed, n_batches, B, V, C=3, N=50, L=20, device="cpu"
     return out
 
 
-def _max_token_id(path):
-    from .data import read_news_parsed
-    t = read_news_parsed(path).titles
-    return int(t.max()) if t.size else 0
-
-
-def _fit_main(a):
-    """The DIR form of the command line: src/train.py's train() on DIR/train
-    (behaviors_parsed.tsv, news_parsed.tsv, optionally
-    pretrained_word_embedding.npy) validated on DIR/val (behaviors.tsv,
-    news_parsed.tsv); one JSON line."""
-    import json
-    import os
-
-    import numpy as np
-
-    from .config import NRMSConfig
-    from .data import read_news_parsed
-    from .fit import ImpressionSet, TrainSet, fit
-    from .nrms import NRMS
-
-    rank, world, _, dev, group = _fed_setup(a)
-    tr, va = os.path.join(a.dir, "train"), os.path.join(a.dir, "val")
-    corpus = read_news_parsed(os.path.join(tr, "news_parsed.tsv"))
-    try:                                       # src/train.py:76-80
-        emb = torch.from_numpy(np.load(os.path.join(tr, "pretrained_word_embedding.npy"))).float()
-        V = emb.shape[0]
-    except FileNotFoundError:
-        emb = None
-        V = int(corpus.titles.max()) + 1 if corpus.titles.size else 1
-        if os.path.exists(os.path.join(va, "news_parsed.tsv")):
-            V = max(V, _max_token_id(os.path.join(va, "news_parsed.tsv")) + 1)
-    has_val = os.path.exists(os.path.join(va, "behaviors.tsv"))
-
-    class Cfg(NRMSConfig):
-        num_words = V
-        hip_train = not a.aten
-        num_epochs = a.epochs if a.epochs is not None else NRMSConfig.num_epochs
-        num_batches_validate = (a.validate_every if a.validate_every is not None
-                                else NRMSConfig.num_batches_validate)
-    if a.negatives == "resample":              # raw behaviors.tsv, negatives drawn per (seed, epoch) on the device
-        k = Cfg.negative_sampling_ratio if a.k is None else a.k
-        if a.export_epoch is not None:
-            ts = ImpressionSet(os.path.join(tr, "behaviors.tsv"), corpus, k=k,
-                               num_clicked=Cfg.num_clicked_news_a_user)
-            ts.export_epoch(a.export_epoch[1], a.seed, int(a.export_epoch[0]))
-            print(json.dumps({"mode": "export", "epoch": int(a.export_epoch[0]), "path": a.export_epoch[1],
-                              "samples": len(ts), "n_dropped": ts.n_dropped, "k": k}))
-            return
-        ts = ImpressionSet(os.path.join(tr, "behaviors.tsv"), corpus, k=k,
-                           num_clicked=Cfg.num_clicked_news_a_user, device=dev)
-        if rank == 0:
-            print(f"Load training dataset with size {len(ts)} ({ts.n_dropped} positives dropped: their impression "
-                  f"has fewer than {k} negatives).", flush=True)
-    else:
-        if a.export_epoch is not None or a.k is not None:
-            raise SystemExit("--export-epoch and --k go with --negatives resample")
-        ts = TrainSet(os.path.join(tr, "behaviors_parsed.tsv"), corpus,
-                      num_clicked=Cfg.num_clicked_news_a_user, device=dev)
-        if rank == 0:
-            print(f"Load training dataset with size {len(ts)}.", flush=True)
-    torch.manual_seed(a.seed)
-    model = NRMS(Cfg, emb).to(dev)
-    fed = FedAvg(model, a.every, group=group) if group is not None else None
-    try:
-        r = fit(model, ts, va if has_val else None, checkpoint_dir=a.checkpoint_dir, seed=a.seed,
-                steps=a.max_steps, batch_size=a.batch, fed=fed)
-    finally:
-        if fed is not None:
-            fed.dist.destroy_process_group()
-    if rank != 0:
-        return
-    out = {"mode": "fit (HIP kernels)" if dev.type == "cuda" and not a.aten else "fit (ATen autograd)",
-           "steps": r.steps, "step": r.step, "start_step": r.start_step, "batch": a.batch,
-           "steps_per_s": r.steps_per_s if r.steps else None, "last_auc": r.last_auc, "best_auc": r.best_auc,
-           "early_stopped": r.early_stopped, "checkpoint": r.checkpoint,
-           "final_loss": float(r.losses[-1]) if r.steps else None}
-    if a.negatives == "resample":
-        out.update({"negatives": "resample", "k": ts.K, "samples": len(ts), "n_dropped": ts.n_dropped})
-    if fed is not None:
-        out.update({"world": world, "fedavg_every": fed.every, "syncs": r.syncs, "shard_sizes": r.shard_sizes,
-                    "fedavg_native": fed.native, "dist_backend": a.dist_backend})
-    print(json.dumps(out), flush=True)
-
-
-def _free_port():
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def _launch_ranks(a):
-    """DIR --gpus N (N > 1) started without a launcher: run
-    torch.distributed.run with N ranks of this command line as a CHILD process
-    (started before this process touches a GPU; the program of this process is
-    never replaced) and return its exit code. The ranks' output goes straight
-    to ours. The nccl (RCCL) backend needs a GPU per rank; gloo may put all
-    ranks on one GPU or on the CPU."""
-    import subprocess
-    import sys
-    if a.dist_backend == "nccl" and torch.cuda.device_count() < a.gpus:
-        print(f"train: --gpus {a.gpus} with the nccl backend needs {a.gpus} GPUs, "
-              f"{torch.cuda.device_count()} visible", file=sys.stderr)
-        return 2
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}",
-           "--master-addr", "127.0.0.1", f"--master-port={_free_port()}",
-           "-m", "newsrecommendationsystem_amd.train", *sys.argv[1:]]
-    return subprocess.run(cmd).returncode
-
-
-def _fed_setup(a):
-    """(rank, world, local rank, device, process group or None) of the DIR
-    form. --gpus N is the world size: without it one process and no group;
-    with it this process is one client (a group even at N = 1, so one GPU
-    exercises the federated route). Fatal: a launcher whose WORLD_SIZE is not
-    N, or nccl with fewer GPUs than ranks."""
-    import os
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank, local = int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
-    gpu = torch.cuda.is_available()
-    if a.gpus is None:
-        dev = torch.device("cuda", 0) if gpu else torch.device("cpu")
-        if gpu:
-            torch.cuda.set_device(dev)
-        return 0, 1, 0, dev, None
-    if world != a.gpus:
-        raise SystemExit(f"train: WORLD_SIZE={world} but --gpus={a.gpus}: the launcher's process count and "
-                         f"--gpus must agree")
-    if a.dist_backend == "nccl" and torch.cuda.device_count() < world:
-        raise SystemExit(f"train: {world} ranks on the nccl backend need {world} GPUs, "
-                         f"{torch.cuda.device_count()} visible")
-    dev = torch.device("cuda", local % torch.cuda.device_count()) if gpu else torch.device("cpu")
-    if gpu:
-        torch.cuda.set_device(dev)
-    import torch.distributed as dist
-    if not dist.is_initialized():
-        if "MASTER_ADDR" not in os.environ:                # --gpus 1 run plainly: a group of one
-            os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
-        kw = {"device_id": dev} if a.dist_backend == "nccl" else {}
-        dist.init_process_group(a.dist_backend, rank=rank, world_size=world, **kw)
-    return rank, world, local, dev, dist.group.WORLD
-
-
-def _bench_main(a):
-    """--bench: the fit loop's device route against its host_batches route and
-    the synthetic train_step loop, alternated on one model in one process, on a
-    generated split (20,000 samples, 1 + K = 3, 50 clicked, V = 70,976, dropout
-    0.2, no validation). Prints the table and writes it to
-    profiles/fit_bench.txt."""
-    import os
-    import tempfile
-    import time
-
-    from .config import NRMSConfig
-    from .data import synthetic_train_split
-    from .fit import TrainSet, fit
-    from .nrms import NRMS
-
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
-    B, steps, pairs = a.batch, a.steps, max(5, a.pairs)
-    S, n_news = 20000, 20000
-
-    class Cfg(NRMSConfig):
-        num_batches_show_loss = 100
-    torch.manual_seed(0)
-    model = NRMS(Cfg, torch.randn(Cfg.num_words, 300)).to(dev)
-    with tempfile.TemporaryDirectory() as d:
-        corpus = synthetic_train_split(d, seed=0, n_samples=S, n_news=n_news, V=Cfg.num_words, K=2)
-        ts = TrainSet(os.path.join(d, "behaviors_parsed.tsv"), corpus, device=dev)
-    syn = synthetic_train_batches(100, steps, B, Cfg.num_words, device=dev)
-    opt = make_optimizer(model)
-    quiet = lambda *_: None
-
-    def leg_device():
-        return fit(model, ts, steps=steps, batch_size=B, log=quiet).steps_per_s
-
-    def leg_host():
-        return fit(model, ts, steps=steps, batch_size=B, log=quiet, host_batches=True).steps_per_s
-
-    def leg_synthetic():
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for cand, clk in syn:
-            train_step(model, opt, cand, clk)
-        torch.cuda.synchronize()
-        return steps / (time.perf_counter() - t0)
-
-    legs = [("fit device", leg_device), ("fit host_batches", leg_host), ("synthetic train_step", leg_synthetic)]
-    fit(model, ts, steps=a.warmup + 20, batch_size=B, log=quiet)                       # warm-up, untimed
-    fit(model, ts, steps=a.warmup + 20, batch_size=B, log=quiet, host_batches=True)
-    for cand, clk in syn[:a.warmup + 20]:
-        train_step(model, opt, cand, clk)
-    rate, med = _alternate(legs, pairs)
-    lines = [f"fit bench: S = {S}, 1+K = 3, N = 50, B = {B}, V = {Cfg.num_words}, dropout "
-             f"{Cfg.dropout_probability}, validation off; {pairs} alternated rounds of {steps} steps per leg, "
-             f"one process, {torch.cuda.get_device_name(dev)}"] + _leg_lines(rate, med)
-    lines.append(f"fit device / synthetic train_step (medians): {med['fit device'] / med['synthetic train_step']:.4f}")
-    lines.append(f"fit device / fit host_batches (medians):     {med['fit device'] / med['fit host_batches']:.4f}")
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    with open(_profile_path("fit_bench.txt", a.bench_out), "w") as f:
-        f.write(text)
-
-
-def _alternate(legs, pairs):
-    """Run the legs [(name, () -> steps/s)] in turn, `pairs` rounds: (name ->
-    its rates in run order, name -> their median)."""
-    import statistics
-    rate = {name: [] for name, _ in legs}
-    for _ in range(pairs):
-        for name, fn in legs:
-            rate[name].append(fn())
-    return rate, {k: statistics.median(v) for k, v in rate.items()}
-
-
-def _leg_lines(rate, med):
-    """The table of _alternate's result: one line per leg."""
-    return ["steps/s per round (in run order):"] + [
-        f"  {name:22s} median {med[name]:7.1f}  range {min(v):7.1f} .. {max(v):7.1f}  "
-        f"[{', '.join(f'{x:.1f}' for x in v)}]" for name, v in rate.items()]
-
-
-def _profile_path(name, override):
-    import os
-    out = override or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", name)
-    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
-    return out
-
-
-def _bench_resample_main(a):
-    """--bench-resample: fit on an ImpressionSet (negatives drawn in the gather
-    launch) against fit on the TrainSet of its exported epoch 0 (the static
-    route), alternated on one model in one process, on a generated raw split
-    (about 20,000 samples, 1 + K = 3, 50 clicked, V = 70,976, dropout 0.2, no
-    validation). Prints the table and writes it to
-    profiles/fit_resample_bench.txt."""
-    import os
-    import tempfile
-
-    from .config import NRMSConfig
-    from .data import read_news_parsed, synthetic_split
-    from .fit import ImpressionSet, TrainSet, fit
-    from .nrms import NRMS
-
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
-    B, steps, pairs = a.batch, a.steps, max(5, a.pairs)
-
-    class Cfg(NRMSConfig):
-        num_batches_show_loss = 100
-    torch.manual_seed(0)
-    model = NRMS(Cfg, torch.randn(Cfg.num_words, 300)).to(dev)
-    with tempfile.TemporaryDirectory() as d:
-        synthetic_split(d, seed=0, n_news=20000, n_users=2000, n_impressions=4800, V=Cfg.num_words)
-        corpus = read_news_parsed(os.path.join(d, "news_parsed.tsv"))
-        iset = ImpressionSet(os.path.join(d, "behaviors.tsv"), corpus, k=2, device=dev)
-        iset.export_epoch(os.path.join(d, "behaviors_parsed.tsv"), 0, 0)
-        ts = TrainSet(os.path.join(d, "behaviors_parsed.tsv"), corpus, device=dev)
-    assert len(ts) == len(iset)
-    quiet = lambda *_: None
-    for s in (ts, iset):                                                # warm-up, untimed
-        fit(model, s, steps=a.warmup + 20, batch_size=B, log=quiet)
-    rate, med = _alternate([(name, lambda s=s: fit(model, s, steps=steps, batch_size=B, log=quiet).steps_per_s)
-                            for name, s in (("fit TrainSet (static)", ts), ("fit ImpressionSet", iset))], pairs)
-    ts_bytes = sum(t.numel() * t.element_size() for t in (ts.titles, ts.rows))
-    lines = [f"fit resample bench: S = {len(iset)} samples of {iset.imp_hist.shape[0]} impressions "
-             f"({iset.neg_rows.shape[0]} negatives, {iset.hist_rows.shape[0]} distinct histories, "
-             f"{iset.n_dropped} positives dropped), 1+K = 3, N = 50, B = {B}, V = {Cfg.num_words}, dropout "
-             f"{Cfg.dropout_probability}, validation off; {pairs} alternated rounds of {steps} steps per leg, "
-             f"one process, {torch.cuda.get_device_name(dev)}"] + _leg_lines(rate, med)
-    lines.append(f"fit ImpressionSet / fit TrainSet (medians): "
-                 f"{med['fit ImpressionSet'] / med['fit TrainSet (static)']:.4f}")
-    lines.append(f"device bytes: TrainSet {ts_bytes} (titles {ts.titles.numel() * 8}, rows {ts.rows.numel() * 4}); "
-                 f"ImpressionSet {iset.device_bytes} (titles {iset.titles.numel() * 8}, "
-                 f"the rest {iset.device_bytes - iset.titles.numel() * 8})")
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    with open(_profile_path("fit_resample_bench.txt", a.bench_out), "w") as f:
-        f.write(text)
-
-
-def _quality_resample_main(a):
-    """--quality-resample: quality.resample_vs_static, one run, written to
-    profiles/resample_quality.txt."""
-    from .quality import resample_vs_static
-    text = resample_vs_static(epochs=a.epochs if a.epochs is not None else 6, B=a.batch, seed=a.seed)
-    print(text, end="")
-    with open(_profile_path("resample_quality.txt", a.bench_out), "w") as f:
-        f.write(text)
-
-
-def _main():
-    """python -m newsrecommendationsystem_amd.train [--steps 20] [--batch 128] [--every 5]
-    Under torch.distributed.run: FedAvg across ranks (config 5 shape); prints
-    one JSON line on rank 0 with steps/s, sync time and the final loss.
-
-    python -m newsrecommendationsystem_amd.train DIR [--checkpoint-dir checkpoint/NRMS] [--seed 0]
-        [--epochs N] [--batch B] [--max-steps n] [--negatives file|resample] [--k K] [--export-epoch E PATH]
-        [--validate-every n] [--gpus N [--every E] [--dist-backend nccl|gloo]]
-    trains on a MIND directory (fit.py; _fit_main). --negatives file (default): DIR/train/
-    behaviors_parsed.tsv with the negatives it lists; resample: DIR/train/behaviors.tsv, K new negatives per
-    positive and epoch (fit.ImpressionSet); --export-epoch E PATH writes epoch E's draw (for --seed) as a
-    behaviors_parsed.tsv and exits. --bench: _bench_main; --bench-resample: _bench_resample_main;
-    --quality-resample: _quality_resample_main. --gpus N: a federated fit (fit(fed=FedAvg)) over N ranks,
-    each a client on the samples of the users it owns, models averaged every E steps; under
-    torch.distributed.run this process is one client, run plainly it starts the N ranks as a child process
-    and waits (_launch_ranks). Rank 0 prints the JSON line (with world, fedavg_every, syncs, shard_sizes)
-    and writes ckpt-{t}.pth; rank r its optimizer state to ckpt-{t}.rank{r}.pth."""
-    import argparse
-    import json
-    import time
-
-    from .config import NRMSConfig
-    from .distributed import init_from_env
-    from .nrms import NRMS
-
-    ap = argparse.ArgumentParser()
-    ap.add_argument("dir", nargs="?", default=None, help="MIND directory (train/ and val/): fit on it")
-    ap.add_argument("--steps", type=int, default=None)
-    ap.add_argument("--batch", type=int, default=None)
-    ap.add_argument("--every", type=int, default=5, help="FedAvg: average the models every E steps")
-    ap.add_argument("--gpus", type=int, default=None,
-                    help="DIR: federated fit over N ranks (started here as a torch.distributed.run child "
-                         "unless a launcher already runs this process)")
-    ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default=None,
-                    help="DIR --gpus: process-group backend (default: nccl on a GPU, gloo on the CPU)")
-    ap.add_argument("--aten", action="store_true", help="ATen autograd + torch Adam instead of HIP")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--checkpoint-dir", default="checkpoint/NRMS")
-    ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--epochs", type=int, default=None)
-    ap.add_argument("--max-steps", type=int, default=None)
-    ap.add_argument("--validate-every", type=int, default=None,
-                    help="DIR: validate (and checkpoint on improvement) every n steps (default: the config's 1000)")
-    ap.add_argument("--bench", action="store_true", help="fit loop: device route vs host_batches vs synthetic")
-    ap.add_argument("--pairs", type=int, default=5)
-    ap.add_argument("--bench-out", default=None)
-    ap.add_argument("--negatives", choices=("file", "resample"), default="file",
-                    help="file: behaviors_parsed.tsv's negatives; resample: behaviors.tsv, new negatives per epoch")
-    ap.add_argument("--k", type=int, default=None, help="negatives per positive with --negatives resample")
-    ap.add_argument("--export-epoch", nargs=2, metavar=("E", "PATH"), default=None,
-                    help="with --negatives resample: write epoch E's samples as a behaviors_parsed.tsv and exit")
-    ap.add_argument("--bench-resample", action="store_true", help="fit loop: ImpressionSet vs exported TrainSet")
-    ap.add_argument("--quality-resample", action="store_true",
-                    help="planted teacher: validation AUC per epoch, static vs resampled negatives")
-    a = ap.parse_args()
-    if a.bench or a.bench_resample:
-        a.steps = 300 if a.steps is None else a.steps
-        a.batch = 64 if a.batch is None else a.batch
-        return _bench_main(a) if a.bench else _bench_resample_main(a)
-    if a.quality_resample:
-        a.batch = 64 if a.batch is None else a.batch
-        return _quality_resample_main(a)
-    a.batch = 128 if a.batch is None else a.batch
-    if a.dir is not None:
-        if a.gpus is not None:
-            import os
-            import sys
-            if a.gpus < 1:
-                ap.error("--gpus must be at least 1")
-            if a.dist_backend is None:
-                a.dist_backend = "nccl" if torch.cuda.is_available() else "gloo"
-            if "WORLD_SIZE" not in os.environ and a.gpus > 1:
-                sys.exit(_launch_ranks(a))                  # no launcher around us: start one
-        return _fit_main(a)
-    a.steps = 20 if a.steps is None else a.steps
-    rank, world, local, distributed = init_from_env()
-    dev = torch.device("cuda", local) if torch.cuda.is_available() else torch.device("cpu")
-    if dev.type == "cuda":
-        torch.cuda.set_device(dev)
-    torch.manual_seed(0)                        # identical initial weights on every rank
-
-    class Cfg(NRMSConfig):
-        hip_train = not a.aten
-    model = NRMS(Cfg, torch.randn(NRMSConfig.num_words, 300)).to(dev)
-    opt = (torch.optim.Adam(model.parameters(), lr=Cfg.learning_rate) if a.aten
-           else make_optimizer(model))
-    fed = FedAvg(model, a.every) if distributed else None
-    batches = synthetic_train_batches(100 + rank, a.steps + a.warmup, a.batch, NRMSConfig.num_words,
-                                      device=dev)
-    for cand, clk in batches[:a.warmup]:
-        train_step(model, opt, cand, clk)
-    batches = batches[a.warmup:]
-    sync_t = 0.0
-    if dev.type == "cuda":
-        torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    loss = None
-    for cand, clk in batches:
-        loss = train_step(model, opt, cand, clk)
-        if fed is not None:
-            if dev.type == "cuda":
-                torch.cuda.synchronize()
-            ts = time.perf_counter()
-            if fed.step() and dev.type == "cuda":
-                torch.cuda.synchronize()
-            sync_t += time.perf_counter() - ts
-    if dev.type == "cuda":
-        torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    if rank == 0:
-        print(json.dumps({"mode": ("train (HIP kernels)" if dev.type == "cuda" and not a.aten
-                                   else "train (ATen autograd)") + " + FedAvg", "world": world, "steps": a.steps,
-                          "batch_per_rank": a.batch, "fedavg_every": a.every,
-                          "steps_per_s": a.steps / dt, "samples_per_s": world * a.batch * a.steps / dt,
-                          "fedavg_sync_s_total": sync_t, "final_loss": float(loss),
-                          "param_bytes": int(sum(p.numel() for p in model.parameters()) * 4)}))
-
-
 if __name__ == "__main__":
+    from .train_cli import _main
     _main()

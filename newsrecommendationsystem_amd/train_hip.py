@@ -192,6 +192,21 @@ def forward_hip(model, cand_ids, clicked_ids, seed):
     return NRMSTrain.apply(model, cand_ids, clicked_ids, p, int(seed), *model_params(model))
 
 
+def hip_dropout_masks(n_rows, D, p, seed, device):
+    """The two dropout masks ([n_rows, D], 0 or 1/(1-p)) of the HIP training
+    step with dropout seed `seed` (nrms_dropout with seed 2s on the embedding
+    output, 2s+1 on the MHSA output), from the same kernel on ones: as
+    train.forward_autograd's `masks` they give it the HIP step's sample."""
+    ones = torch.ones(n_rows * D, device=device)
+    out = []
+    for s in (2 * int(seed), 2 * int(seed) + 1):
+        mk = torch.empty_like(ones)
+        N.call("nrms_dropout", N.ptr(ones), N.ptr(mk), ones.numel(), ctypes.c_float(p), ctypes.c_uint64(s),
+               N.stream_handle(device))
+        out.append(mk.view(n_rows, D))
+    return out
+
+
 class _AdamTensor(ctypes.Structure):
     """nrms_adam_tensor_t (include/nrms_hip.h)."""
     _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
