@@ -73,7 +73,12 @@ extern "C" {
  *    ABI 9, added later (additive, no bump): nrms_train_batch_gather and
  *    nrms_xent_class0 (the fit loop's batch assembly and fused loss).
  *    ABI 9, added later (additive, no bump): nrms_train_batch_sample_gather
- *    (batch assembly from raw impressions, negatives drawn in the launch). */
+ *    (batch assembly from raw impressions, negatives drawn in the launch).
+ *    ABI 9, added later (additive, no bump): nrms_views_weights_t,
+ *    nrms_views_state_size, nrms_views_prepare,
+ *    nrms_news_views_fuse_workspace_size, nrms_news_views_fuse and
+ *    nrms_rows_add_position (the Exp1 model's category views and position
+ *    embedding, csrc/views.hip). */
 #define NRMS_ABI_VERSION 9
 
 typedef enum {
@@ -549,6 +554,73 @@ int32_t nrms_forward_prepared_timed(const int64_t* cand_ids, const int64_t* clic
                                     int32_t proj_mode, float* logits, void* workspace, size_t workspace_bytes,
                                     hipStream_t stream, const nrms_forward_state_t* state,
                                     hipEvent_t* stage_events, int32_t n_events);
+
+/* ---------------------------------------------------------------------------
+ * (ABI 9, added later) The Exp1 model (src/model/Exp1/): NRMS plus a category
+ * and a subcategory view of every article, pooled with the title vector by a
+ * second additive attention, and a learned position embedding added to the
+ * user history before its self-attention. Eval mode. The title encoder, the
+ * user encoder and the scorers are the NRMS entry points above; these three
+ * add what Exp1 has on top (csrc/views.hip).
+ *
+ * Element encoders (news_encoder.py:36-43): view(id) = relu(emb[id] W^T + b).
+ * The reference shares one embedding table between both; emb_cat and emb_sub
+ * may be the same pointer. final_attention is an AdditiveAttention over the
+ * stacked views [title, category, subcategory] (news_encoder.py:104-110). */
+typedef struct {
+  const float* emb_cat; const float* emb_sub; int64_t n_cat; int32_t emb_dim;  /* [C, E] each; the reference shares one table */
+  const float* w_cat; const float* b_cat;     /* [D, E], [D] */
+  const float* w_sub; const float* b_sub;     /* [D, E], [D] */
+  const float* w_fin; const float* b_fin; const float* q_fin;  /* final_attention: [Q, D], [Q], [Q] */
+  int32_t d_model; int32_t query_dim;
+} nrms_views_weights_t;
+
+/* The weight-derived state: for every id c in [0, C)
+ *   cat_vec[c] = relu(emb_cat[c] W_cat^T + b_cat), sub_vec[c] likewise, and
+ *   each row's final-attention logit q_fin . tanh(W_fin v + b_fin),
+ * laid out in `state` as floats: cat_vec[C, D], sub_vec[C, D], cat_logit[C],
+ * sub_logit[C] (nrms_views_state_size bytes; 16-byte aligned). Id 0 is an
+ * ordinary row (padding_idx only affects gradients). fp32 FMA chains; a ReLU
+ * zero is an exact +0. The state is invalid once any field of w changes: the
+ * caller prepares again. One launch, nothing allocated, no synchronisation.
+ * Limits: E + D <= 12,280, Q <= 208, C <= 2^24 (else NRMS_ERR_UNSUPPORTED; the
+ * size function: 0). Null pointers, n_cat < 0 or a non-positive dimension:
+ * NRMS_ERR_INVALID_ARG; a short state buffer: NRMS_ERR_WORKSPACE. */
+size_t nrms_views_state_size(int64_t n_cat, int32_t D);
+int32_t nrms_views_prepare(const nrms_views_weights_t* w, void* state, size_t state_bytes, hipStream_t stream);
+
+/* NewsEncoder.forward after the title encoder (news_encoder.py:95-111), for n
+ * articles: title_vec[n, D] (the title encoder's output), category[n] and
+ * subcategory[n] ids, state from nrms_views_prepare under the same w.
+ *   logit_t = q_fin . tanh(W_fin title_vec[r] + b_fin)   (exact-f32 MFMA GEMM
+ *             in every arithmetic mode; one float per row in the workspace)
+ *   (w_t, w_c, w_s) = softmax(logit_t, cat_logit[cat], sub_logit[sub]),
+ *             the maximum subtracted first
+ *   out[r] = (w_t title_vec[r] + w_c cat_vec[cat]) + w_s sub_vec[sub]
+ * out == title_vec is allowed and bitwise equal to the out-of-place call. A
+ * category or subcategory outside [0, C) gives a NaN row and is never read
+ * through; a title vector holding NaN gives a NaN row; no other row changes.
+ * D % 4 == 0, Q <= 208, title_vec / state / out 16-byte aligned (else
+ * NRMS_ERR_UNSUPPORTED). Two launches, nothing allocated. */
+size_t nrms_news_views_fuse_workspace_size(int64_t n);
+int32_t nrms_news_views_fuse(const float* title_vec, int64_t n, const int64_t* category,
+                             const int64_t* subcategory, const nrms_views_weights_t* w, const void* state,
+                             float* out, void* workspace, size_t workspace_bytes, hipStream_t stream);
+
+/* UserEncoder's position embedding (user_encoder.py:27-28) into a contiguous
+ * out[B, N, D]: out[b, i, :] = x[b, i, :] + pos[i, :], pos[N, D].
+ *   rows != NULL: x[b, i] = src[rows[b * N + i]], a gather from the
+ *     [n_src_rows, D] table src (the eval path's news-vector table); a row
+ *     outside [0, n_src_rows) gives a NaN row and is never read through.
+ *   rows == NULL: src is a [B, N, D] view, element (b, i, d) at
+ *     src[b * stride_b + i * stride_n + d] (strides in floats, >= 0): the
+ *     views nrms_user_encode takes, the transpose(0, 1) one included.
+ * One fp32 add per element: bitwise torch's x + P. 16-byte lanes when D % 4 ==
+ * 0, src / pos / out are 16-byte aligned and (view form) the strides are
+ * multiples of 4; scalar lanes otherwise, same result. N * D < 2^31. */
+int32_t nrms_rows_add_position(const float* src, int64_t n_src_rows, const int64_t* rows, int64_t B,
+                               int32_t N, int64_t stride_b, int64_t stride_n, const float* pos, int32_t D,
+                               float* out, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Training kernels: the train-mode forward pieces and the backward of the path

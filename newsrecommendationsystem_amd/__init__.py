@@ -3,8 +3,9 @@ Maguire1999/NewsRecommendationSystem's ``model.NRMS``).
 
     from newsrecommendationsystem_amd import NRMS, NRMSConfig
 """
-from .config import BaseConfig, NRMSConfig  # noqa: F401
+from .config import BaseConfig, Exp1Config, NRMSConfig  # noqa: F401
 from .nrms import NRMS  # noqa: F401
+from .exp1 import Exp1  # noqa: F401
 from .fit import ImpressionSet, TrainSet, fit  # noqa: F401
 
-__all__ = ["NRMS", "NRMSConfig", "BaseConfig", "fit", "TrainSet", "ImpressionSet"]
+__all__ = ["NRMS", "NRMSConfig", "Exp1", "Exp1Config", "BaseConfig", "fit", "TrainSet", "ImpressionSet"]

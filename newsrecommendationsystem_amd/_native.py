@@ -50,6 +50,16 @@ class FlatTensor(ctypes.Structure):
     _fields_ = [("data", _p), ("numel", _i64), ("offset", _i64)]
 NRMS_STATE_FOLDED_TABLE, NRMS_STATE_QKV_PACKS, NRMS_STATE_ADD_PACKS = 1, 2, 4
 
+
+class ViewsWeights(ctypes.Structure):
+    """nrms_views_weights_t (the Exp1 model's element encoders and final attention)."""
+    _fields_ = [("emb_cat", _p), ("emb_sub", _p), ("n_cat", _i64), ("emb_dim", _i32),
+                ("w_cat", _p), ("b_cat", _p), ("w_sub", _p), ("b_sub", _p),
+                ("w_fin", _p), ("b_fin", _p), ("q_fin", _p), ("d_model", _i32), ("query_dim", _i32)]
+
+
+_VW = ctypes.POINTER(ViewsWeights)
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "nrms_abi_version": (_i32, []),
@@ -89,6 +99,12 @@ SIGNATURES = {
     "nrms_rank_impressions": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p]),
     "nrms_recommend_topk_workspace_size": (_sz, [_i64, _i64, _i32, _i32, _i32]),
     "nrms_recommend_topk": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _p, _p, _p, _sz, _p]),
+    # Exp1: category views and position embedding (views.hip)
+    "nrms_views_state_size": (_sz, [_i64, _i32]),
+    "nrms_views_prepare": (_i32, [_VW, _p, _sz, _p]),
+    "nrms_news_views_fuse_workspace_size": (_sz, [_i64]),
+    "nrms_news_views_fuse": (_i32, [_p, _i64, _p, _p, _VW, _p, _p, _p, _sz, _p]),
+    "nrms_rows_add_position": (_i32, [_p, _i64, _p, _i64, _i32, _i64, _i64, _p, _i32, _p, _p]),
     # training kernels
     "nrms_dropout": (_i32, [_p, _p, _i64, ctypes.c_float, ctypes.c_uint64, _p]),
     "nrms_additive_forward_train": (_i32, [_p, _i64, _i32, _EW, _p, _p, _p, _p]),

@@ -36,10 +36,25 @@ def load(path, map_location="cpu"):
 def load_model(path, device="cpu"):
     """The checkpoint's model on `device`, in eval mode: an NRMS whose
     num_words and word_embedding_dim are the saved embedding table's shape
-    (the other hyper-parameters are NRMSConfig's)."""
-    from .config import NRMSConfig
+    (the other hyper-parameters are NRMSConfig's). A state dict that holds
+    news_encoder.text_encoders.title.word_embedding.weight is a
+    MODEL_NAME=Exp1 checkpoint and gives an Exp1, with num_words,
+    num_categories and num_clicked_news_a_user from the saved shapes."""
+    from .config import Exp1Config, NRMSConfig
     from .nrms import NRMS
     state = load(path)["model_state_dict"]
+    pre = "news_encoder.text_encoders.title."
+    if pre + "word_embedding.weight" in state:
+        from .exp1 import Exp1
+        V, D = state[pre + "word_embedding.weight"].shape
+        C, E = state["news_encoder.element_encoders.category.embedding.weight"].shape
+        n_clicked = state["user_encoder.position_embedding"].shape[0]
+        cfg = type("CheckpointCfg", (Exp1Config,), dict(
+            num_words=int(V), word_embedding_dim=int(D), num_categories=int(C), category_embedding_dim=int(E),
+            num_clicked_news_a_user=int(n_clicked)))
+        model = Exp1(cfg)
+        model.load_state_dict(state)
+        return model.to(torch.device(device)).eval()
     V, D = state["news_encoder.word_embedding.weight"].shape
     cfg = type("CheckpointCfg", (NRMSConfig,), dict(num_words=int(V), word_embedding_dim=int(D)))
     model = NRMS(cfg)

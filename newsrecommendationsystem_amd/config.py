@@ -36,3 +36,12 @@ class NRMSConfig(BaseConfig):
     hip_proj_mode = 0            # 0 auto, 1 direct, 2 folded (include/nrms_hip.h)
     hip_cache_folded_table = True  # reuse the vocab projection across get_news_vector calls
     hip_check_ids = True         # raise IndexError on out-of-range ids, like nn.Embedding
+
+
+class Exp1Config(NRMSConfig):
+    """src/config.py:98-106: NRMS plus the category and subcategory of every
+    article and a position embedding of the history (exp1.py). The build
+    knobs are NRMSConfig's: the title encoder is the NRMS news encoder."""
+    dataset_attributes = {"news": ["category", "subcategory", "title"], "record": []}
+    num_attention_heads = 15
+    ensemble_factor = 1

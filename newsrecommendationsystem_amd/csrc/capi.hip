@@ -555,6 +555,64 @@ int32_t nrms_score_pairs(const float* news, int64_t n_news, const float* user, i
   return launch_score_pairs(news, n_news, user, n_users, news_idx, user_idx, n_pairs, D, out, stream);
 }
 
+// ---- Exp1: category views and position embedding (views.hip)
+static int32_t views_weights_status(const nrms_views_weights_t* w) {
+  if (!w) return NRMS_ERR_INVALID_ARG;
+  if (w->n_cat < 0 || w->emb_dim <= 0 || w->d_model <= 0 || w->query_dim <= 0) return NRMS_ERR_INVALID_ARG;
+  if (!w->emb_cat || !w->emb_sub || !w->w_cat || !w->b_cat || !w->w_sub || !w->b_sub || !w->w_fin || !w->b_fin ||
+      !w->q_fin)
+    return NRMS_ERR_INVALID_ARG;
+  if (w->n_cat > ((int64_t)1 << 24) || w->query_dim > kQMax || (int64_t)w->emb_dim + w->d_model > 12280)
+    return NRMS_ERR_UNSUPPORTED;
+  return NRMS_OK;
+}
+
+size_t nrms_views_state_size(int64_t n_cat, int32_t D) {
+  if (n_cat < 0 || n_cat > ((int64_t)1 << 24) || D <= 0 || D > 12280) return 0;
+  return (size_t)n_cat * (2 * (size_t)D + 2) * sizeof(float);
+}
+
+int32_t nrms_views_prepare(const nrms_views_weights_t* w, void* state, size_t state_bytes, hipStream_t stream) {
+  if (int32_t st = views_weights_status(w)) return st;
+  if (w->n_cat == 0) return NRMS_OK;
+  if (!state) return NRMS_ERR_INVALID_ARG;
+  if (state_bytes < nrms_views_state_size(w->n_cat, w->d_model)) return NRMS_ERR_WORKSPACE;
+  return launch_views_prepare(*w, static_cast<float*>(state), stream);
+}
+
+size_t nrms_news_views_fuse_workspace_size(int64_t n) {
+  return n <= 0 ? 0 : align_up((size_t)n * sizeof(float));
+}
+
+int32_t nrms_news_views_fuse(const float* title_vec, int64_t n, const int64_t* category,
+                             const int64_t* subcategory, const nrms_views_weights_t* w, const void* state,
+                             float* out, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (n < 0) return NRMS_ERR_INVALID_ARG;
+  if (int32_t st = views_weights_status(w)) return st;
+  if (n == 0) return NRMS_OK;
+  if (!title_vec || !category || !subcategory || !state || !out) return NRMS_ERR_INVALID_ARG;
+  if (!workspace || workspace_bytes < nrms_news_views_fuse_workspace_size(n)) return NRMS_ERR_WORKSPACE;
+  if (w->d_model % 4 != 0 || (uintptr_t)title_vec % 16 || (uintptr_t)state % 16 || (uintptr_t)out % 16 ||
+      (uintptr_t)w->w_fin % 16 || (uintptr_t)workspace % 4)
+    return NRMS_ERR_UNSUPPORTED;
+  float* logit = static_cast<float*>(workspace);
+  int32_t st = launch_gemm_additive_score(title_vec, n, w->d_model, w->w_fin, w->b_fin, w->q_fin, w->query_dim,
+                                          logit, stream);
+  if (st) return st;
+  return launch_views_combine(title_vec, logit, n, category, subcategory, static_cast<const float*>(state),
+                              w->n_cat, w->d_model, out, stream);
+}
+
+int32_t nrms_rows_add_position(const float* src, int64_t n_src_rows, const int64_t* rows, int64_t B,
+                               int32_t N, int64_t stride_b, int64_t stride_n, const float* pos, int32_t D,
+                               float* out, hipStream_t stream) {
+  if (B < 0 || N <= 0 || D <= 0 || n_src_rows < 0 || stride_b < 0 || stride_n < 0) return NRMS_ERR_INVALID_ARG;
+  if (B == 0) return NRMS_OK;
+  if (!src || !pos || !out) return NRMS_ERR_INVALID_ARG;
+  if ((int64_t)N * D > INT32_MAX || B > INT32_MAX / (int64_t)N) return NRMS_ERR_UNSUPPORTED;
+  return launch_rows_add_position(src, n_src_rows, rows, B, N, stride_b, stride_n, pos, D, out, stream);
+}
+
 size_t nrms_recommend_topk_workspace_size(int64_t n_users, int64_t n_news, int32_t D, int32_t K,
                                           int32_t n_excl) {
   if (n_users < 0 || n_news < 0 || n_news > INT32_MAX || D != 300 || K < 1 || K > 256 || n_excl < 0 ||

@@ -518,5 +518,17 @@ int32_t launch_rank_impressions(const float* news, int64_t n_news, const float* 
                                 hipStream_t s);
 int32_t launch_score(const float* news, int64_t B, int C, int64_t sb, int64_t sc,
                      const float* user, int64_t su, int D, float* out, hipStream_t s);
+// Exp1's view kernels (views.hip); the contracts are nrms_views_prepare's,
+// nrms_news_views_fuse's and nrms_rows_add_position's (nrms_hip.h). state:
+// cat_vec [C, D], sub_vec [C, D], cat_logit [C], sub_logit [C].
+size_t views_prepare_lds_bytes(int E, int D);
+int32_t launch_views_prepare(const nrms_views_weights_t& w, float* state, hipStream_t s);
+// D % 4 == 0; title / state / out 16-B aligned; title == out allowed
+int32_t launch_views_combine(const float* title, const float* title_logit, int64_t n, const int64_t* category,
+                             const int64_t* subcategory, const float* state, int64_t C, int D, float* out,
+                             hipStream_t s);
+int32_t launch_rows_add_position(const float* src, int64_t n_src_rows, const int64_t* rows, int64_t B, int N,
+                                 int64_t stride_b, int64_t stride_n, const float* pos, int D, float* out,
+                                 hipStream_t s);
 
 }  // namespace nrms

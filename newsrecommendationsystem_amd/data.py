@@ -33,18 +33,33 @@ class NewsCorpus:
     reference keeps the first vector per id, src/evaluate.py:197-201).
     `numeric` (optional): the ids' numbers when every id is "N<digits>"
     without a leading zero (the native reader's parse; numeric_news_index
-    then skips its string pass)."""
+    then skips its string pass). `path` (optional): the file the corpus was
+    read from, where categories() finds the category columns."""
 
-    def __init__(self, ids, titles, numeric=None):
+    def __init__(self, ids, titles, numeric=None, path=None):
         self.ids = list(ids)
         self.titles = np.ascontiguousarray(titles, dtype=np.int64)
         self.numeric = numeric
+        self.path = path
+        self._categories = None
         self.index = {}
         for i, nid in enumerate(self.ids):
             self.index.setdefault(nid, i)
 
     def __len__(self):
         return len(self.ids)
+
+    def categories(self):
+        """(category, subcategory) int64 [n] each, row-aligned with titles:
+        read from `path` on first need (only a model with category views asks)."""
+        if self._categories is None:
+            if self.path is None:
+                raise ValueError("this NewsCorpus was not read from a news_parsed.tsv: no category columns")
+            cat, sub = read_news_categories(self.path)
+            if len(cat) != len(self.ids):
+                raise ValueError(f"{self.path}: {len(cat)} category rows for {len(self.ids)} articles")
+            self._categories = (cat, sub)
+        return self._categories
 
 
 def _parse_titles(cells, ids, num_words_title):
@@ -101,10 +116,11 @@ def read_news_parsed(path, num_words_title=NUM_WORDS_TITLE):
     """news_parsed.tsv -> NewsCorpus: the native reader for the plain MIND
     form, else the csv module + _parse_titles (every form the reference's
     pandas reader takes as a plain tab-separated table)."""
-    fast = read_news_parsed_native(path, num_words_title)
-    if fast is not None:
-        return fast
-    return read_news_parsed_py(path, num_words_title)
+    corpus = read_news_parsed_native(path, num_words_title)
+    if corpus is None:
+        corpus = read_news_parsed_py(path, num_words_title)
+    corpus.path = path
+    return corpus
 
 
 def read_news_parsed_py(path, num_words_title=NUM_WORDS_TITLE):
@@ -117,6 +133,22 @@ def read_news_parsed_py(path, num_words_title=NUM_WORDS_TITLE):
             ids.append(row[ci])
             cells.append(row[ct])
     return NewsCorpus(ids, _parse_titles(cells, ids, num_words_title))
+
+
+def read_news_categories(path):
+    """(category, subcategory) of news_parsed.tsv as int64 arrays, one entry
+    per row in file order (row-aligned with read_news_parsed's titles): the
+    integer columns src/data_preprocess.py:201-223 writes and src/dataset.py
+    reads for models with category views. csv module (the general path)."""
+    cat, sub = [], []
+    with open(path, newline="") as f:
+        rd = csv.reader(f, delimiter="\t", quoting=csv.QUOTE_NONE)
+        header = next(rd)
+        cc, cs = header.index("category"), header.index("subcategory")
+        for row in rd:
+            cat.append(int(row[cc]))
+            sub.append(int(row[cs]))
+    return np.array(cat, dtype=np.int64), np.array(sub, dtype=np.int64)
 
 
 class Impression:
@@ -487,14 +519,21 @@ def read_behaviors_parsed(path, corpus, num_clicked=NUM_CLICKED):
 
 
 # ---------------------------------------------------------------- writers
-def write_news_parsed(path, ids, titles):
+def write_news_parsed(path, ids, titles, categories=None, subcategories=None):
+    """news_parsed.tsv with the given titles and, when passed, category /
+    subcategory columns (ints, one per article); an omitted column is all 0."""
+    n = len(ids)
+    cats = [0] * n if categories is None else [int(c) for c in categories]
+    subs = [0] * n if subcategories is None else [int(c) for c in subcategories]
+    if len(cats) != n or len(subs) != n:
+        raise ValueError(f"{n} ids with {len(cats)} categories and {len(subs)} subcategories")
     with open(path, "w", newline="") as f:
         w = csv.writer(f, delimiter="\t", quoting=csv.QUOTE_NONE, escapechar="\\", lineterminator="\n")
         w.writerow(["id", "category", "subcategory", "title", "abstract", "title_entities",
                     "abstract_entities"])
         zero_a = str([0] * 50)
-        for nid, t in zip(ids, titles):
-            w.writerow([nid, 0, 0, "[" + ", ".join(str(int(x)) for x in t) + "]", zero_a,
+        for nid, c, s, t in zip(ids, cats, subs, titles):
+            w.writerow([nid, c, s, "[" + ", ".join(str(int(x)) for x in t) + "]", zero_a,
                         str([0] * len(t)), zero_a])
 
 

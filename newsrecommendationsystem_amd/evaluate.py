@@ -60,33 +60,59 @@ class EvalPlan:
         return len(self.offsets) - 1
 
 
+def has_category_views(model):
+    """The model's news encoder reads category and subcategory besides the title (exp1.Exp1)."""
+    return hasattr(getattr(model, "news_encoder", None), "element_encoders")
+
+
+def category_args(model, corpus):
+    """news_vectors' keyword arguments besides the titles: none for an NRMS
+    model (its call is unchanged); for a model with category views the
+    corpus's (category, subcategory) columns, read on first need."""
+    return {"categories": corpus.categories()} if has_category_views(model) else {}
+
+
 @torch.no_grad()
-def news_vectors(model, titles, chunk=65536):
-    """[n + 1, D] news-vector table on the model's device; last row = PADDED_NEWS."""
+def news_vectors(model, titles, chunk=65536, categories=None):
+    """[n + 1, D] news-vector table on the model's device; last row = PADDED_NEWS.
+    categories: (category [n], subcategory [n]) for a model with category
+    views (category_args), passed along in every chunk."""
     ne = model.news_encoder
     dev = ne.word_embedding.weight.device
     D = ne.word_embedding.embedding_dim
     n = titles.shape[0]
     out = torch.zeros(n + 1, D, dtype=torch.float32, device=dev)
     t = torch.from_numpy(titles) if isinstance(titles, np.ndarray) else titles
+    if has_category_views(model):
+        if categories is None:
+            raise ValueError("a model with category views needs the corpus's categories (category_args)")
+        cat, sub = (torch.as_tensor(c) for c in categories)
     for a in range(0, n, chunk):
         b = min(n, a + chunk)
-        out[a:b] = model.get_news_vector({"title": t[a:b]})
+        news = {"title": t[a:b]}
+        if has_category_views(model):
+            news.update(category=cat[a:b], subcategory=sub[a:b])
+        out[a:b] = model.get_news_vector(news)
     return out
 
 
 @torch.no_grad()
 def user_vectors(model, news_tab, hist_rows, chunk=16384):
     """User vectors of every history: gather clicked rows (PADDED -> zero row)
-    then the HIP UserEncoder."""
+    then the HIP UserEncoder. A user encoder with a position embedding
+    (exp1.UserEncoder) adds it in the gather's pass."""
     dev = news_tab.device
     U, Nc = hist_rows.shape
     D = news_tab.shape[1]
     out = torch.empty(U, D, dtype=torch.float32, device=dev)
     rows = torch.from_numpy(hist_rows).to(dev)
+    ue = model.user_encoder
     for a in range(0, U, chunk):
         r = rows[a:a + chunk].contiguous()
         b = r.shape[0]
+        if hasattr(ue, "add_position_rows"):
+            out[a:a + b] = ue.encode_positioned(ue.add_position_rows(news_tab, r))
+            continue
         x = torch.empty(b * Nc, D, dtype=torch.float32, device=dev)
         N.call("nrms_embedding_gather", N.ptr(r), b * Nc, N.ptr(news_tab), news_tab.shape[0], D,
                N.ptr(x), N.stream_handle(dev))
@@ -98,7 +124,7 @@ def user_vectors(model, news_tab, hist_rows, chunk=16384):
 def score_plan(model, plan):
     """Logits of every (impression, candidate) pair and the per-impression
     metric table [n_imp, 4] (AUC, MRR, nDCG@5, nDCG@10; fp64) on the device."""
-    news_tab = news_vectors(model, plan.corpus.titles)
+    news_tab = news_vectors(model, plan.corpus.titles, **category_args(model, plan.corpus))
     dev = news_tab.device
     D = news_tab.shape[1]
     users = user_vectors(model, news_tab, plan.hist_rows)

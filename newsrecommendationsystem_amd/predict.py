@@ -36,7 +36,7 @@ import torch
 
 from . import _native as N
 from .data import BehaviorsTable, load_behaviors_any, read_news_parsed
-from .evaluate import news_vectors, user_vectors
+from .evaluate import category_args, news_vectors, user_vectors
 from .splits import index_split
 
 TIES = {"order": N.NRMS_RANK_ORDER, "shared": N.NRMS_RANK_SHARED}
@@ -122,7 +122,7 @@ def predict_plan(model, plan, ties="order"):
     nrms_rank_impressions call."""
     if not plan.n_impressions:
         return Predictions([], [0], np.zeros(0, np.int32), np.zeros(0, np.float32))
-    news_tab = news_vectors(model, plan.corpus.titles)
+    news_tab = news_vectors(model, plan.corpus.titles, **category_args(model, plan.corpus))
     users = user_vectors(model, news_tab, plan.hist_rows)
     scores, ranks = rank_impressions(news_tab, users, plan.cand, plan.imp_user, plan.offsets, ties)
     return Predictions(plan.impression_ids, plan.offsets, ranks.cpu().numpy(), scores.cpu().numpy())

@@ -31,7 +31,7 @@ import torch
 
 from . import _native as N
 from .data import BehaviorsTable, load_behaviors, read_news_parsed
-from .evaluate import news_vectors, user_vectors
+from .evaluate import category_args, news_vectors, user_vectors
 from .splits import history_rows_of as history_rows   # (corpus, hists, num_clicked): EvalPlan's hist_rows
 
 MAX_K = 256
@@ -136,7 +136,7 @@ def recommend_split(model, corpus, impressions, k=10, exclude_history=True):
     k = int(k)
     if not users:
         return Recommendations([], np.zeros((0, k), np.int64), np.zeros((0, k), np.float32), corpus.ids)
-    news_tab = news_vectors(model, corpus.titles)
+    news_tab = news_vectors(model, corpus.titles, **category_args(model, corpus))
     uvec = user_vectors(model, news_tab, hrows)
     rows, scores = topk(news_tab, uvec, k, exclude=hrows if exclude_history else None, n_news=len(corpus))
     return Recommendations(users, _host(rows).astype(np.int64), _host(scores).astype(np.float32), corpus.ids)
